@@ -11,8 +11,8 @@ BASELINE.json configs[1] per GPU -- 256 concurrent games x 400 sims/move, 10-blo
 ResNet, 14x14 STANDARD start, random-init weights (torch.manual_seed(0)), synthetic data.
 MFMA operand type: fp16 by default -- it is the 16-bit type that meets north_star's float bar (logits
 within 1e-3 of the reference's fp32 net.py: 3.1e-4, tests/test_net_gpu.py) at the same MFMA rate;
-configs[1]'s bf16 does not (2.3e-3) and is measured right after the timed region and reported beside
-the headline as `alt_dtype_bf16` with both measured errors in `float_parity`.
+configs[1]'s bf16 does not (2.3e-3); with --full it is measured right after the timed region and reported
+beside the headline as `alt_dtype_bf16` with both measured errors in `float_parity`.
 N > 1: one process per GPU -- started by this script itself (`python bench.py --gpus N`: the parent makes no
 torch / HIP call, spawns the N ranks with the torchrun environment and exits non-zero if any of them fails) or by
 `python -m torch.distributed.run ... bench.py --gpus N` -- games sharded 256/GPU (weak scaling), no data-path
@@ -23,12 +23,18 @@ A communicator that cannot be set up at --backend nccl stops the job (no silent 
 
 Prints ONE JSON line (rank 0).  `roofline` prices the dominant kernel group (the MFMA
 implicit-GEMM network forward) with HIP events recorded on the engine's own stream during the
-timed steps (every 16th simulation step carries the events; on every step the five of them cost 2.7 %); `cpu_baseline`
-times the CPU oracle (oracle/, test infrastructure) + PyTorch-CPU ResNet on a bounded sample of the
-same workload on this box's host cores (N = 1 only).  `value` is measured with the full
-policy head unless --policy-head legal is given (the reference's softmax -> mask -> renormalise arithmetic, op for op); after the timed
-region three more steps run with the opt-in legal-only policy head and are reported separately as
-`alt_policy_head_legal_only` -- never as `value`.
+timed steps (every 16th simulation step carries the events; on every step the five of them cost 2.7 %).
+`value` is measured with the full policy head unless --policy-head legal is given (the reference's
+softmax -> mask -> renormalise arithmetic, op for op).  `ms_per_step` is the wall time of one timed step.
+
+A plain run does only that: set-up, warm-up, the timed steps, the line.  --dump-outputs DIR also writes
+what the last timed step computed as .npy files (dump_outputs below; the inputs are seeded, so two runs
+with the same arguments see the same positions).  --full adds the side measurements behind the timed
+region (N = 1 only where noted): three steps with the opt-in legal-only policy head
+(`alt_policy_head_legal_only`, DESIGN.md 4.2 -- never `value`), the other 16-bit operand type
+(`alt_dtype_*`) with `float_parity` (N = 1), the drop-in surface (`dropin`, N = 1), `cpu_baseline` -- the CPU
+oracle (oracle/, test infrastructure) + PyTorch-CPU ResNet on a bounded sample of the same workload on this
+box's host cores (N = 1) -- and the two rocprofv3 --pmc child passes that count `roofline.traffic` (N = 1).
 """
 import argparse
 import json
@@ -126,7 +132,17 @@ def parse_args(argv=None):
     ap.add_argument("--launch-dry-run", action="store_true",
                     help="N>1 without an external launcher: start the N ranks, have each report its environment and exit (no GPU, no torch)")
     ap.add_argument("--launch-timeout", type=float, default=3000.0, help="seconds the self-launcher waits for its ranks")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what is reported beside the headline: the legal-only policy head, the other 16-bit operand type "
+                         "and float_parity, the drop-in surface, the CPU baselines and the live rocprofv3 --pmc traffic passes "
+                         "(the --no-* options above then skip single ones); without it a run does only the headline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32 / float64)")
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:
+        args.no_alt_policy_head = args.no_alt_dtype = args.no_dropin = args.no_cpu_baseline = args.no_live_traffic = True
     preset = {"1": (400, 10, 128, 256, 14), "3": (800, 20, 256, 256, 14), "ref": (50, 15, 256, 100, 8)}[args.config or "1"]
     args.sims = preset[0] if args.sims is None else args.sims
     args.blocks = preset[1] if args.blocks is None else args.blocks
@@ -327,6 +343,7 @@ def main():
         state["host_s"] += t_d - t_c
         state["enqueue_s"] += t_b - t_a
         state["plies"] += 1
+        state["last"] = (res, flats)
         return int(res["sims_done"].sum())
 
     def sync():
@@ -396,6 +413,8 @@ def main():
     if exchange["ranks_seen"] != world:
         print("bench.py: tuples of %d ranks arrived, world is %d" % (exchange["ranks_seen"], world), file=sys.stderr, flush=True)
         sys.exit(4)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, state["last"], boards, [r for r in recs if r["ply"] == state["step"] - 1 and r["game"] % world == 0])
 
     # Reported beside the headline, never as `value`: the same job with the opt-in legal-only policy head
     # (fpc_set_policy_mode(FPC_POLICY_LEGAL)): the policy Linear is evaluated only at
@@ -567,6 +586,42 @@ def main():
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
+
+
+def dump_outputs(d, last, boards, recs, max_games=2048):
+    """--dump-outputs: what the last timed step handed its caller -- the search results (root visit count, simulations
+    made, every root child's move / visits / prior / W), the move drawn per game, the positions the next step starts
+    from -- and the training tuples that step collected (z as the episode end set it), by game id.  Integers and
+    bytes are stored exactly as float64 / float32: about 15 kB per game (3.4 MB at configs[1]); above `max_games` games
+    a fixed sample of that many (seed 0) keeps the files under 30 MB."""
+    import fpc_ffi
+    res, flats = last
+    G = len(flats)
+    rows = np.arange(G) if G <= max_games else np.sort(np.random.default_rng(0).choice(G, max_games, replace=False))
+    recs = sorted(recs, key=lambda r: r["game"])
+    if G > max_games:
+        recs = [recs[i] for i in rows if i < len(recs)]
+    n = len(recs)
+    t_meta = np.zeros((n, 5), np.float64)             # game id, ply, side to move, z, number of pi entries
+    t_mailbox = np.zeros((n, len(recs[0]["mailbox"]) if n else 0), np.float32)
+    t_flat = np.full((n, fpc_ffi.MAX_TUPLE_C), -1.0, np.float64)
+    t_visits = np.zeros_like(t_flat)
+    for i, r in enumerate(recs):
+        k = len(r["flat"])
+        t_meta[i] = (r["game"], r["ply"], r["turn"], r["z"], k)
+        t_mailbox[i] = r["mailbox"]
+        t_flat[i, :k] = r["flat"]
+        t_visits[i, :k] = r["visits"]
+    arrays = {"root_n": res["root_n"].astype(np.float64), "sims_done": res["sims_done"].astype(np.float64),
+              "n_children": res["n_children"].astype(np.float64), "child_flat": res["flat"].astype(np.float64),
+              "child_visits": res["visits"].astype(np.float64), "child_prior": res["prior"].astype(np.float32),
+              "child_w": res["w"].astype(np.float64), "move_flat": np.asarray(flats).astype(np.float64),
+              "next_boards": np.asarray(boards).astype(np.float32)}
+    arrays = {k: v[rows] for k, v in arrays.items()}
+    arrays.update({"tuple_meta": t_meta, "tuple_mailbox": t_mailbox, "tuple_flat": t_flat, "tuple_visits": t_visits})
+    os.makedirs(d, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), a)
 
 
 def dropin_measure(model, R, G, sims, dt, plies=3):

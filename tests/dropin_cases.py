@@ -161,37 +161,13 @@ def _host_tree_search(az, game_type, games, evaluator, C, sims):
     return roots
 
 
-def _load_reference_mcts():
-    """the reference's OWN src/py/mcts.py (only where /root/reference exists: the build container), bound to our
-    shim: `alphazero_cpp` resolves to alphazero-4-player-chess_amd/alphazero_cpp.py; its one foreign import
-    (line_profiler_pycharm.profile, a PyCharm plugin) gets an identity decorator"""
-    import importlib.util
-    import os
-    import sys
-    import types
-    path = "/root/reference/src/py/mcts.py"
-    if not os.path.exists(path):
-        return None
-    if "line_profiler_pycharm" not in sys.modules:
-        stub = types.ModuleType("line_profiler_pycharm")
-        stub.profile = lambda f: f
-        sys.modules["line_profiler_pycharm"] = stub
-    spec = importlib.util.spec_from_file_location("reference_mcts_py", path)
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-def case_host_tree(backend, R, max_cases=3, max_sims=100, use_reference_mcts=False):
+def case_host_tree(backend, R, max_cases=3, max_sims=100):
     """Golden MCTS.search cases of the real reference, re-run through the HOST forms of Node (tree bookkeeping
     in the shim, board operations through the engine's C-ABI): root and second-level visit counts must match
-    the reference bit for bit; with use_reference_mcts the loop that runs IS the reference's own mcts.py."""
+    the reference bit for bit."""
     az = setup(backend, R)
     from fen_parser import parse_board_args_from_fen
     from four_player_chess_board import FourPlayerChess
-    ref_mod = _load_reference_mcts() if use_reference_mcts else None
-    if use_reference_mcts and ref_mod is None:
-        return -1
     g = gold(R)
     done = 0
     for rec in g["searches"]:
@@ -203,11 +179,7 @@ def case_host_tree(backend, R, max_cases=3, max_sims=100, use_reference_mcts=Fal
         if start_pl != rec["before"][0]["pl"] or int(game.GetTurn().GetColor()) != rec["before"][0]["turn"]:
             continue                        # a case that does not start from the start position
         ev = Eval(rec["kind"], R)
-        if ref_mod is not None:
-            m = ref_mod.MCTS(FourPlayerChess, ev, {"C": rec["C"], "num_searches": rec["sims"], "pool_size": 10})
-            roots = m.search([game])
-        else:
-            roots = _host_tree_search(az, FourPlayerChess, [game], ev, rec["C"], rec["sims"])
+        roots = _host_tree_search(az, FourPlayerChess, [game], ev, rec["C"], rec["sims"])
         ref = rec["roots"][0]
         assert roots[0].GetVisitCount() == ref["root_n"]
         assert [[c.GetMoveMade().GetFlatIndex(), c.GetVisitCount()] for c in roots[0].GetChildren()] == [[c[0], c[1]] for c in ref["children"]]

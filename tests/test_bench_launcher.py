@@ -94,3 +94,45 @@ def test_workload_labels_follow_the_arguments():
     a = bench.parse_args(["--blocks", "20", "--hidden", "256", "--sims", "800"])
     assert bench.workload_label(a.games, a.sims, a.blocks, a.hidden, a.board).startswith("configs[3]:")
     assert bench.workload_label(256, 400, 10, 128, 8).startswith("custom")
+
+
+def test_a_plain_run_measures_the_headline_only():
+    sys.path.insert(0, REPO)
+    import bench
+    side = ("no_alt_policy_head", "no_alt_dtype", "no_dropin", "no_cpu_baseline", "no_live_traffic")
+    a = bench.parse_args(["--steps", "7"])
+    assert a.steps == 7 and not a.full and a.dump_outputs is None and all(getattr(a, k) for k in side)
+    a = bench.parse_args(["--full"])
+    assert a.full and not any(getattr(a, k) for k in side)
+    a = bench.parse_args(["--full", "--no-dropin"])
+    assert a.no_dropin and not a.no_alt_dtype
+    p = subprocess.run([sys.executable, BENCH, "--steps", "0"], capture_output=True, text=True, timeout=120)
+    assert p.returncode != 0 and "--steps" in p.stderr
+
+
+def test_dump_outputs_writes_float_arrays_of_the_last_step(tmp_path):
+    """bench.dump_outputs on arrays shaped like a configs[1] step: float32 / float64 only, integers exact, tuples by game
+    id, and a fixed sample of games above max_games"""
+    import numpy as np
+    sys.path.insert(0, REPO)
+    import bench
+    G, rng = 256, np.random.default_rng(5)
+    res = {"root_n": np.full(G, 401, np.int32), "sims_done": np.full(G, 400, np.int32), "n_children": np.full(G, 3, np.int32),
+           "flat": rng.integers(0, 23520, (G, 256)).astype(np.int32), "visits": rng.integers(0, 400, (G, 256)).astype(np.int32),
+           "prior": rng.random((G, 256)).astype(np.float32), "w": rng.random((G, 256))}
+    flats, boards = rng.integers(0, 23520, G), rng.integers(0, 256, (G, 288)).astype(np.uint8)
+    recs = [{"mailbox": np.full(196, g % 256, np.uint8), "turn": g % 4, "z": 0.5, "flat": np.arange(3), "visits": np.array([5, 0, 7]),
+             "game": g, "ply": 9} for g in reversed(range(G))]
+    bench.dump_outputs(str(tmp_path / "a"), (res, flats), boards, recs)
+    files = {f[:-4]: np.load(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")}
+    assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) < 64 << 20
+    assert np.array_equal(files["child_visits"], res["visits"]) and np.array_equal(files["next_boards"], boards)
+    assert np.array_equal(files["move_flat"], flats) and np.array_equal(files["tuple_meta"][:, 0], np.arange(G))
+    assert np.array_equal(files["tuple_visits"][:, :4], np.tile([5, 0, 7, 0], (G, 1)))
+    big = 3000
+    res = {k: np.repeat(v[:1], big, axis=0) for k, v in res.items()}
+    bench.dump_outputs(str(tmp_path / "b"), (res, np.arange(big)), np.zeros((big, 288), np.uint8), recs, max_games=1000)
+    bench.dump_outputs(str(tmp_path / "c"), (res, np.arange(big)), np.zeros((big, 288), np.uint8), recs, max_games=1000)
+    mb, mc = np.load(tmp_path / "b" / "move_flat.npy"), np.load(tmp_path / "c" / "move_flat.npy")
+    assert mb.shape == (1000,) and np.array_equal(mb, mc) and np.all(np.diff(mb) > 0)

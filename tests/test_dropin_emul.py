@@ -38,15 +38,6 @@ def test_host_node_forms_reproduce_reference_searches():
     assert dc.case_host_tree("emul", 8, max_cases=2, max_sims=100) >= 1
 
 
-def test_the_reference_mcts_py_itself_runs_on_the_shim():
-    """VERDICT r2, missing #4: the reference's own src/py/mcts.py (imported from /root/reference where that exists,
-    never copied) driving OUR alphazero_cpp shim -- same golden visit counts."""
-    n = dc.case_host_tree("emul", 8, max_cases=2, max_sims=100, use_reference_mcts=True)
-    if n < 0:
-        pytest.skip("/root/reference is not present on this machine")
-    assert n >= 1
-
-
 @pytest.mark.parametrize("R", [8, 14])
 def test_play_loop_takes_successors_from_one_batched_prefetch(R):
     assert dc.case_play_loop_prefetch("emul", R) >= 6

@@ -9,6 +9,7 @@ TAG=${1:-rXX}
 PART=${2:-AB}      # A: default stats + PMC passes (both networks); B: configs[3] / 8x8 / arena / memory-side PMC / power / default run
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 mkdir -p gpurun_out/$TAG
+RUN=$_          # the folder just made: this round's files
 stats() {   # stats <name> <bench flags...>
   name=$1; shift
   rm -rf gpurun_out/prof_$name
@@ -39,7 +40,7 @@ python3 tools/arena_bench.py > gpurun_out/$TAG/arena_1024.json 2> gpurun_out/$TA
 bash tools/pmc_fc_mem.sh > gpurun_out/$TAG/pmc_fc_mem.log 2>&1; tail -12 gpurun_out/$TAG/pmc_fc_mem.log | cut -c1-400
 for p in a b c d e f; do cp gpurun_out/pmcm_$p/*/*counter_collection.csv gpurun_out/$TAG/pmcm_$p.csv 2>/dev/null; done
 bash tools/power_probe.sh --no-alt-dtype > gpurun_out/$TAG/power_probe.log 2>&1; cp gpurun_out/power_samples.txt gpurun_out/$TAG/power_samples.txt; tail -3 gpurun_out/$TAG/power_probe.log | cut -c1-300
-python3 bench.py > gpurun_out/$TAG/default_run.json 2> gpurun_out/$TAG/default_run.err; cut -c1-200 gpurun_out/$TAG/default_run.json
+python3 bench.py --full > $RUN/default_run.json 2> $RUN/default_run.err; cut -c1-200 $RUN/default_run.json   # with every side measurement
 # round 5: the micro-benchmarks DESIGN.md 4.2 / 9 quote (build here if the binaries did not travel with the snapshot)
 [ -x tools/micro/fc_stream ] && [ -x tools/micro/mfma_sustained ] || make -s -C tools/micro fc_stream mfma_sustained
 timeout -k 10 120 tools/micro/mfma_sustained 1.0 > gpurun_out/$TAG/mfma_sustained.log 2>&1; cat gpurun_out/$TAG/mfma_sustained.log | cut -c1-200
