@@ -39,8 +39,8 @@ class AlphaZero:
     def play(self):
         G = int(self.args["num_parallel_games"])
         games = [self._new_game() for _ in range(G)]
-        # same (games, sims, dtype) request as MCTS.search makes, so the handle is not re-created under us
-        eng = az.engine(G, int(self.args["num_searches"]), self.mcts.nn_dtype if self.mcts._native else None)
+        # same (rows = games x leaves_per_step, sims, dtype) request as MCTS.search makes, so the handle is not re-created under us
+        eng = az.engine(self.mcts.engine_rows(G), int(self.args["num_searches"]), self.mcts.nn_dtype if self.mcts._native else None)
         L = int(self.args["max_game_length"])
         uniforms = torch.rand(L, G, generator=self.gen, dtype=torch.float64).tolist()
 

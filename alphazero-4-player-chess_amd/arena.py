@@ -89,9 +89,11 @@ def summary(games):
             "plies": sum(len(g.plies) for g in games)}
 
 
-def nn_search_fn(eng, sims, c_puct):
-    """search over the engine's internal MFMA ResNet (weights already loaded into `eng`)."""
+def nn_search_fn(eng, sims, c_puct, leaves=1, virtual_loss=1.0):
+    """search over the engine's internal MFMA ResNet (weights already loaded into `eng`); leaves > 1: leaf-parallel
+    search (fpc_search_set_leaves), `eng` needs leaves x games rows."""
     def fn(pods):
+        eng.set_leaves(leaves, virtual_loss)
         eng.search_begin(pods, c_puct)
         eng.search_run(sims)
         return eng.search_results(roots=pods)

@@ -60,6 +60,14 @@ struct fpc_engine {
   int *d_rc_meta = nullptr;       // [max_games][3]
   size_t rc_cap = 0;
   long sims_issued = 0;           // simulation steps since fpc_search_begin (bounded by max_sims: pools + log table)
+  // ---- leaf-parallel search (fpc_search_set_leaves)
+  int leaves = 1;                 // leaves per game of the NEXT selection
+  double vl = 1.0;                // virtual loss per pending visit
+  int *d_VL = nullptr;            // [max_games][node_cap] pending visits, allocated on the first leaves > 1
+  bool stepping = false;          // between fpc_search_begin and fpc_search_results
+  bool multi = false;             // this search runs the leaf-parallel kernels (leaves > 1 at begin, or set during it)
+  int rows_k = 1;                 // leaves per game of the selection waiting to be expanded (rows = rows_k * G)
+  bool pending_vl = false;        // that selection was made by a leaf-parallel kernel: its paths hold pending visits
   // ---- training tuples (device resident until the episode ends) and their RCCL exchange
   fpc_tuple *d_tuples = nullptr;
   int tuple_cap = 0, tuple_count = 0;
@@ -467,6 +475,9 @@ int fpc_search_begin(fpc_engine *e, const fpc_board *roots, int n_games, double 
   if (!e || !roots || n_games < 1) return fail(e, FPC_EINVAL, "bad argument");
   USE_DEV(e);
   if (n_games > e->cfg.max_games) return fail(e, FPC_EINVAL, "n_games %d > max_games %d", n_games, e->cfg.max_games);
+  if ((long)e->leaves * n_games > e->cfg.max_games)
+    return fail(e, FPC_EINVAL, "%d leaves x %d games = %ld rows > max_games %d (fpc_search_set_leaves)", e->leaves, n_games,
+                (long)e->leaves * n_games, e->cfg.max_games);
   if (e->t.noise && e->noise_n != n_games)
     return fail(e, FPC_EINVAL, "root noise was uploaded for %d games, this search has %d: call fpc_search_set_root_noise again (or with NULL)", e->noise_n, n_games);
   int r;
@@ -478,19 +489,42 @@ int fpc_search_begin(fpc_engine *e, const fpc_board *roots, int n_games, double 
   HIPCHK(e, hipGetLastError());
   e->searching = true;
   e->sims_issued = 0;
+  e->stepping = true;
+  e->multi = e->leaves > 1;
+  e->rows_k = 1;
+  e->pending_vl = false;
+  if (e->multi) {     // leaf-parallel from the start: the roots' counters (children are zeroed where they are created)
+    FPC_LAUNCH(k_vl_roots, (n_games + 63) / 64, 64, e->stream, e->d_VL, e->t.node_cap, n_games);
+    HIPCHK(e, hipGetLastError());
+  }
+  return 0;
+}
+
+static LeafPar leafpar(const fpc_engine *e) { return LeafPar{e->d_VL, e->vl}; }
+
+// every call that selects leaves checks that the rows fit (the setting may have changed after fpc_search_results)
+static int check_rows(fpc_engine *e) {
+  if ((long)e->leaves * e->G > e->cfg.max_games)
+    return fail(e, FPC_EINVAL, "%d leaves x %d games = %ld rows > max_games %d (fpc_search_set_leaves)", e->leaves, e->G,
+                (long)e->leaves * e->G, e->cfg.max_games);
   return 0;
 }
 
 static int launch_select(fpc_engine *e) {
   mark(e, 0);
-  FPC_LAUNCH(k_select, e->G, 64, e->stream, e->dc, e->t, e->G, e->Cpuct, (const double *)e->d_logtab);
+  if (e->multi)
+    FPC_LAUNCH(k_select_multi, e->G, 64, e->stream, e->dc, e->t, e->G, e->leaves, e->Cpuct, (const double *)e->d_logtab, leafpar(e));
+  else
+    FPC_LAUNCH(k_select, e->G, 64, e->stream, e->dc, e->t, e->G, e->Cpuct, (const double *)e->d_logtab);
+  e->rows_k = e->multi ? e->leaves : 1;
+  e->pending_vl = e->multi;
   return 0;
 }
 
-// softmax chunk statistics of logits that did not come from the internal policy Linear
+// softmax chunk statistics of logits that did not come from the internal policy Linear (one record set per row)
 static void launch_partials(fpc_engine *e, const float *logits_dev) {
-  const int nchunks = (e->dc.A / 4 + SM_THREADS - 1) / SM_THREADS;
-  FPC_LAUNCH(k_softmax_partials, e->G * nchunks, SM_THREADS, e->stream, logits_dev, e->dc.A, e->G, nchunks, e->d_stats);
+  const int nchunks = (e->dc.A / 4 + SM_THREADS - 1) / SM_THREADS, rows = e->rows_k * e->G;
+  FPC_LAUNCH(k_softmax_partials, rows * nchunks, SM_THREADS, e->stream, logits_dev, e->dc.A, rows, nchunks, e->d_stats);
 }
 
 // after a k_expand_select launch the leaves it selected become the current ones
@@ -500,15 +534,19 @@ static void swap_leaf_arrays(fpc_engine *e) {
   std::swap(e->t.leaf_turn, e->t.leaf_turn_nx);
 }
 
+// the leaf-parallel kernels leave the GLOBAL pool index g*board_cap + slot in leaf_slot: the encoders read it with stride 0
+static int leaf_board_stride(const fpc_engine *e) { return e->multi ? 0 : e->t.board_cap; }
+
 static int finish_select(fpc_engine *e, int *n_live, const float **enc_dev) {
-  FPC_LAUNCH(k_encode, e->G, 64, e->stream, e->dc, (const fpc_board *)e->t.boards, e->t.board_cap,
-             (const int *)e->t.leaf_slot, (const int *)e->t.leaf_turn, e->G, 0, e->d_enc_f32, (uint16_t *)nullptr,
+  const int rows = e->rows_k * e->G;
+  FPC_LAUNCH(k_encode, rows, 64, e->stream, e->dc, (const fpc_board *)e->t.boards, leaf_board_stride(e),
+             (const int *)e->t.leaf_slot, (const int *)e->t.leaf_turn, rows, 0, e->d_enc_f32, (uint16_t *)nullptr,
              (uint16_t)0, -1);
   HIPCHK(e, hipGetLastError());
   mark(e, 1);
   e->stats.launches_select++;
-  std::vector<int> slots(e->G);
-  HIPCHK(e, hipMemcpyAsync(slots.data(), e->t.leaf_slot, (size_t)e->G * sizeof(int), hipMemcpyDeviceToHost, e->stream));
+  std::vector<int> slots(rows);
+  HIPCHK(e, hipMemcpyAsync(slots.data(), e->t.leaf_slot, (size_t)rows * sizeof(int), hipMemcpyDeviceToHost, e->stream));
   HIPCHK(e, hipStreamSynchronize(e->stream));
   int live = 0;
   for (int s : slots) live += s >= 0;
@@ -520,8 +558,10 @@ static int finish_select(fpc_engine *e, int *n_live, const float **enc_dev) {
 int fpc_search_select(fpc_engine *e, int *n_live, const float **enc_dev) {
   if (!e || !e->searching) return fail(e, FPC_ESTATE, "fpc_search_begin has not been called");
   USE_DEV(e);
-  if (e->sims_issued + 1 > e->cfg.max_sims) return fail(e, FPC_ECAPACITY, "more than max_sims = %d simulations since fpc_search_begin", e->cfg.max_sims);
-  e->sims_issued += 1;
+  int r;
+  if ((r = check_rows(e))) return r;
+  if (e->sims_issued + e->leaves > e->cfg.max_sims) return fail(e, FPC_ECAPACITY, "more than max_sims = %d simulations since fpc_search_begin", e->cfg.max_sims);
+  e->sims_issued += e->leaves;
   launch_select(e);
   return finish_select(e, n_live, enc_dev);
 }
@@ -530,14 +570,30 @@ int fpc_search_expand_select(fpc_engine *e, const float *logits_dev, const float
   if (!e || !e->searching) return fail(e, FPC_ESTATE, "fpc_search_begin has not been called");
   USE_DEV(e);
   if (!logits_dev || !value_dev) return fail(e, FPC_EINVAL, "null logits/value");
-  if (e->sims_issued + 1 > e->cfg.max_sims) return fail(e, FPC_ECAPACITY, "more than max_sims = %d simulations since fpc_search_begin", e->cfg.max_sims);
-  e->sims_issued += 1;
+  int r;
+  if ((r = check_rows(e))) return r;
+  if (e->sims_issued + e->leaves > e->cfg.max_sims) return fail(e, FPC_ECAPACITY, "more than max_sims = %d simulations since fpc_search_begin", e->cfg.max_sims);
+  e->sims_issued += e->leaves;
   mark(e, 3);
   launch_partials(e, logits_dev);
-  FPC_LAUNCH(k_expand_select, e->G, EXPAND_THREADS, e->stream, e->dc, e->t, e->G, (LogitSrc{logits_dev, nullptr, nullptr, 0, 0, 0, 0, 256}),
-             (const float *)e->d_stats, value_dev, e->Cpuct, (const double *)e->d_logtab);
+  const LogitSrc src{logits_dev, nullptr, nullptr, 0, 0, 0, 0, 256};
+  if (e->pending_vl) {
+    FPC_LAUNCH(k_expand_select_multi, e->G, EXPAND_THREADS, e->stream, e->dc, e->t, e->G, e->rows_k, e->leaves, src, (const float *)e->d_stats,
+               value_dev, e->Cpuct, (const double *)e->d_logtab, leafpar(e));
+    swap_leaf_arrays(e);
+  } else if (!e->multi) {
+    FPC_LAUNCH(k_expand_select, e->G, EXPAND_THREADS, e->stream, e->dc, e->t, e->G, src, (const float *)e->d_stats, value_dev, e->Cpuct,
+               (const double *)e->d_logtab);
+    swap_leaf_arrays(e);
+  } else {
+    // a one-leaf selection made before fpc_search_set_leaves switched this search to leaf-parallel: its path holds no
+    // pending visit, so it is expanded by k_expand, and the next step's leaves are selected by k_select_multi
+    FPC_LAUNCH(k_expand, e->G, EXPAND_THREADS, e->stream, e->dc, e->t, e->G, src, (const float *)e->d_stats, value_dev);
+    FPC_LAUNCH(k_select_multi, e->G, 64, e->stream, e->dc, e->t, e->G, e->leaves, e->Cpuct, (const double *)e->d_logtab, leafpar(e));
+  }
   HIPCHK(e, hipGetLastError());
-  swap_leaf_arrays(e);
+  e->rows_k = e->multi ? e->leaves : 1;
+  e->pending_vl = e->multi;
   mark(e, 4);
   e->stats.launches_expand++;
   mark(e, 0);
@@ -550,10 +606,92 @@ int fpc_search_expand(fpc_engine *e, const float *logits_dev, const float *value
   if (!logits_dev || !value_dev) return fail(e, FPC_EINVAL, "null logits/value");
   mark(e, 3);
   launch_partials(e, logits_dev);
-  FPC_LAUNCH(k_expand, e->G, EXPAND_THREADS, e->stream, e->dc, e->t, e->G, (LogitSrc{logits_dev, nullptr, nullptr, 0, 0, 0, 0, 256}), (const float *)e->d_stats, value_dev);
+  const LogitSrc src{logits_dev, nullptr, nullptr, 0, 0, 0, 0, 256};
+  if (e->pending_vl)
+    FPC_LAUNCH(k_expand_multi, e->G, EXPAND_THREADS, e->stream, e->dc, e->t, e->G, e->rows_k, src, (const float *)e->d_stats, value_dev, leafpar(e));
+  else                                       // one leaf per game, or a one-leaf selection made before the switch
+    FPC_LAUNCH(k_expand, e->G, EXPAND_THREADS, e->stream, e->dc, e->t, e->G, src, (const float *)e->d_stats, value_dev);
   HIPCHK(e, hipGetLastError());
   mark(e, 4);
   e->stats.launches_expand++;
+  return 0;
+}
+
+#ifndef FPC_EMUL
+// fpc_search_run of a leaf-parallel search: ceil(sims / K) steps of K leaves per game, the last one of the remainder.
+// Step s: [k_select_multi] -> network over k_s * G rows -> k_expand(_legal)_multi, fused with the next step's selection
+// (k_expand(_legal)_select_multi) for all but the last step.
+static int run_multi(fpc_engine *e, int sims) {
+  const int K = e->leaves, steps = (sims + K - 1) / K, G = e->G;
+  auto leaves_of = [&](int s) { return s + 1 < steps ? K : sims - K * (steps - 1); };
+  const bool legal = e->policy_mode == FPC_POLICY_LEGAL;
+  for (int s = 0; s < steps; ++s) {
+    const int ks = leaves_of(s), rows = ks * G;
+    if (s == 0) {
+      mark(e, 0);
+      FPC_LAUNCH(k_select_multi, G, 64, e->stream, e->dc, e->t, G, ks, e->Cpuct, (const double *)e->d_logtab, leafpar(e));
+    } else {
+      mark(e, 0);
+    }
+    if (e->nn.takes_boards())
+      e->nn.set_board_input((const fpc_board *)e->t.boards, 0, (const int *)e->t.leaf_slot, (const int *)e->t.leaf_turn);
+    else
+      FPC_LAUNCH(k_encode, rows, 64, e->stream, e->dc, (const fpc_board *)e->t.boards, 0, (const int *)e->t.leaf_slot,
+                 (const int *)e->t.leaf_turn, rows, 1, (float *)nullptr, e->nn.input16(), e->nn.one16(), -1);
+    mark(e, 1);
+    e->nn.mark_fn = [](void *ctx, int tag) { mark((fpc_engine *)ctx, tag); };
+    e->nn.mark_ctx = e;
+    int r = legal ? e->nn.forward_legal(rows, e->t, &e->err) : e->nn.forward(rows, false, &e->err);
+    e->nn.mark_fn = nullptr;
+    if (r) return r;
+    mark(e, 3);
+    const bool fuse = s + 1 < steps;
+    const int knext = fuse ? leaves_of(s + 1) : 0;
+    if (legal) {
+      if (fuse)
+        FPC_LAUNCH(k_expand_legal_select_multi, G, 64, e->stream, e->dc, e->t, G, ks, knext, (const float *)e->nn.legal_logits(),
+                   (const float *)e->nn.value(), e->Cpuct, (const double *)e->d_logtab, leafpar(e));
+      else
+        FPC_LAUNCH(k_expand_legal_multi, G, 64, e->stream, e->dc, e->t, G, ks, (const float *)e->nn.legal_logits(), (const float *)e->nn.value(),
+                   leafpar(e));
+    } else {
+      if (fuse)
+        FPC_LAUNCH(k_expand_select_multi, G, EXPAND_THREADS, e->stream, e->dc, e->t, G, ks, knext, e->nn.logit_src(false),
+                   (const float *)e->nn.stats(), (const float *)e->nn.value(), e->Cpuct, (const double *)e->d_logtab, leafpar(e));
+      else
+        FPC_LAUNCH(k_expand_multi, G, EXPAND_THREADS, e->stream, e->dc, e->t, G, ks, e->nn.logit_src(false), (const float *)e->nn.stats(),
+                   (const float *)e->nn.value(), leafpar(e));
+    }
+    if (fuse) swap_leaf_arrays(e);
+    mark(e, 4);
+    e->stats.launches_select++; e->stats.launches_nn++; e->stats.launches_expand++;
+  }
+  e->rows_k = 1;
+  e->pending_vl = false;
+  HIPCHK(e, hipGetLastError());
+  return 0;
+}
+#endif
+
+int fpc_search_set_leaves(fpc_engine *e, int leaves, double virtual_loss) {
+  if (!e) return fail(e, FPC_EINVAL, "null engine");
+  if (leaves < 1 || leaves > FPC_MAX_LEAVES) return fail(e, FPC_EINVAL, "leaves %d outside 1..%d", leaves, FPC_MAX_LEAVES);
+  if (!std::isfinite(virtual_loss) || virtual_loss < 0.0) return fail(e, FPC_EINVAL, "virtual_loss must be finite and >= 0");
+  if (e->stepping && (long)leaves * e->G > e->cfg.max_games)   // a running search; every selection re-checks (check_rows)
+    return fail(e, FPC_EINVAL, "%d leaves x %d games = %ld rows > max_games %d", leaves, e->G, (long)leaves * e->G, e->cfg.max_games);
+  USE_DEV(e);
+  if (leaves > 1 && !e->d_VL) {
+    int r;
+    if ((r = dalloc(e, &e->d_VL, (size_t)e->cfg.max_games * e->t.node_cap))) return r;
+  }
+  if (leaves > 1 && e->searching && !e->multi) {
+    // a search that started with one leaf per game: its nodes were created without pending-visit counters (a pending
+    // one-leaf selection holds none either: fpc_search_expand(_select) expands it with k_expand)
+    HIPCHK(e, hipMemsetAsync(e->d_VL, 0, (size_t)e->cfg.max_games * e->t.node_cap * sizeof(int), e->stream));
+    e->multi = true;
+  }
+  e->leaves = leaves;
+  e->vl = virtual_loss;
   return 0;
 }
 
@@ -561,12 +699,15 @@ int fpc_search_run(fpc_engine *e, int sims) {
   if (!e || !e->searching) return fail(e, FPC_ESTATE, "fpc_search_begin has not been called");
   USE_DEV(e);
   if (sims < 0 || sims > e->cfg.max_sims) return fail(e, FPC_EINVAL, "sims %d > max_sims %d", sims, e->cfg.max_sims);
+  int rc;
+  if ((rc = check_rows(e))) return rc;
   if (e->sims_issued + sims > e->cfg.max_sims) return fail(e, FPC_ECAPACITY, "more than max_sims = %d simulations since fpc_search_begin", e->cfg.max_sims);
   e->sims_issued += sims;
 #ifdef FPC_EMUL
   return fail(e, FPC_EWEIGHTS, "the internal ResNet exists only in the gfx950 build");
 #else
   if (!e->nn.loaded) return fail(e, FPC_EWEIGHTS, "fpc_load_weights has not been called");
+  if (e->multi) return run_multi(e, sims);
   // step s: [k_select] -> network -> k_expand; for all but the last step of this call the expansion and the
   // NEXT step's selection are one launch (k_expand_select), so a step is 4 dependent kernels instead of 5
   for (int s = 0; s < sims; ++s) {
@@ -652,6 +793,7 @@ int fpc_search_results(fpc_engine *e, fpc_board *roots_out, int *root_visits, in
   }
   (void)nodes;
   e->stats.sims += sims;
+  e->stepping = false;
   return err_to_status(e, errs, "game");
 }
 

@@ -11,6 +11,8 @@
 //   k_expand         ParseActionspace / mask / renormalise from those statistics, BackpropagateNodes,
 //                    ExpandNodes                                                        (mcts.py:67-89)
 //   k_expand_select  k_expand of simulation step s + k_select of step s+1 in one launch
+//   k_select_multi / k_expand(_legal)(_select)_multi  the same for the opt-in leaf-parallel search (K leaves per game
+//                    per step, virtual loss; fpc_search_set_leaves): the descent is select_game's, row k*G + g per leaf
 //
 // Reference semantics (file:line relative to /root/reference/src/cpp) are restated per function.
 // Nothing here is translated from the reference: its board is a pointer-rich mailbox + std::vector
@@ -21,6 +23,8 @@
 #pragma once
 #include "fpc_platform.h"
 #include "../../include/fpc_engine.h"
+
+#include <type_traits>
 
 namespace fpc {
 
@@ -245,6 +249,9 @@ __device__ __forceinline__ int wave_list_erase_append(uint8_t *list, int len, in
 // mover's castling rights and a rook leaving its home square clears that side's.
 // Wave-cooperative and wave-uniform: every lane derives the same scalars from the LDS board, the piece
 // lists are edited one entry per lane, lane 0 writes the scalars.  All lanes must call.
+// LEAF_PARALLEL: a separate instance for the leaf-parallel selection, so that the one-leaf kernels' callees -- and with
+// them the compiler's inlining decisions and the kernels' ISA -- stay exactly what they were before leaf-parallel search
+template <bool LEAF_PARALLEL = false>
 __device__ inline bool make_move_wave(fpc_board *b, int from, int to, const DevCfg &c) {
   const int lane = lane_id();
   if (to == FPC_NO_SQ) return false;
@@ -707,6 +714,8 @@ __device__ inline void walk_castle(const fpc_board *b, const DevCfg &c, int from
 //              s->nlegal, and apply the reordering of its full make/undo loop.  Skipped when
 //              do_result found a terminal position (ChooseLeaf returns before the mask is built).
 // `player` < 0 -> side to move.  All lanes of the wave must call this (uniform control flow).
+// LEAF_PARALLEL: see make_move_wave
+template <bool LEAF_PARALLEL = false>
 __device__ inline void wave_position_ops(WaveLds *s, const DevCfg &c, bool do_result, bool do_legal, int player) {
   const int lane = lane_id();
   fpc_board *b = &s->b;
@@ -1247,9 +1256,29 @@ __device__ __forceinline__ void backprop_path(const Tree &t, size_t nb, int g, f
   }
 }
 
+// Leaf-parallel search (fpc_search_set_leaves, K leaves per game per step): row r = k*G + g holds the k-th leaf game g
+// selected in this step.  VL [G][node_cap] counts the pending visits of a node (0 outside a step); the descent sees
+// N' = N + VL and W' = W -+ vl*VL (lower Q on pending paths), a descent that ends on a pending leaf is a collision.
+struct LeafPar {
+  int *VL;
+  double vl;
+};
+struct OneLeaf { int k, G; };   // select_game's context for one leaf per game (never dereferenced: that instance is the one-leaf selection)
+struct LeafRow {         // ... and for descent k of a leaf-parallel step
+  LeafPar lp;
+  int k, G;
+  bool live;             // out: the row is live
+  int leaf_vl, best_vl, cvl;   // the descent's pending-visit counts: node it stands on, best child so far, this lane's child
+};
+
 // One game's selection step, executed by one wave (all 64 lanes call; `s` is the wave's LDS image).
-// The chosen leaf goes to leaf_node/leaf_slot/leaf_turn, or to their _nx twins when `to_next`.
-__device__ inline void select_game(WaveLds &s, const DevCfg &c, const Tree &t, int g, double Cpuct, const double *logtab, bool to_next) {
+// The chosen leaf goes to leaf_node/leaf_slot/leaf_turn, or to their _nx twins when `to_next`, at index g.
+// MULTI (leaf-parallel, descent k of G games): the per-leaf outputs go to row k*G + g; effective statistics, collision
+// check, leaf_slot holds the GLOBAL pool index g*board_cap + slot, VL += 1 along the path of a live row.
+// M: OneLeaf (m null), or LeafRow (leaf-parallel; m->live is set when the row is live).
+template <class M, bool MULTI = !std::is_same<M, OneLeaf>::value>
+__device__ inline void select_game(WaveLds &s, const DevCfg &c, const Tree &t, int g, double Cpuct, const double *logtab, bool to_next, M *m) {
+#define FPC_ROW (MULTI ? m->k * m->G + g : g)     // the leaf's row (folded to g for one leaf per game)
   const int lane = lane_id();
   int *const leaf_node = to_next ? t.leaf_node_nx : t.leaf_node;
   int *const leaf_slot = to_next ? t.leaf_slot_nx : t.leaf_slot;
@@ -1262,8 +1291,9 @@ __device__ inline void select_game(WaveLds &s, const DevCfg &c, const Tree &t, i
   int c0 = t.child0[nb], nc = t.nch[nb], Nn = t.N[nb];
   int slot = t.bslot[nb], parent_slot = -1;        // board-pool slot of node n / of its parent
   const int nboards0 = t.nboards[g];
+  if constexpr (MULTI) { m->leaf_vl = m->lp.VL[nb]; Nn += m->leaf_vl; }
   if (!is_alive) {                          // root already removed from the search (Q5)
-    if (lane == 0) { leaf_node[g] = -1; leaf_slot[g] = -1; }
+    if (lane == 0) { leaf_node[FPC_ROW] = -1; leaf_slot[FPC_ROW] = -1; }
     return;
   }
   // ---- descent: SelectChild (node.cpp:49-78)
@@ -1274,7 +1304,7 @@ __device__ inline void select_game(WaveLds &s, const DevCfg &c, const Tree &t, i
   // be requested as soon as the argmax is known, and at the leaf its slot, its parent's and its move are at hand.
   int n = 0, depth = 0, leaf_mv = 0xffff;
   bool fail = false;
-  int *path = t.path + (size_t)g * t.path_cap;
+  int *path = t.path + (size_t)FPC_ROW * t.path_cap;
   for (;;) {
     if (lane == 0 && depth < t.path_cap) path[depth] = n;
     ++depth;
@@ -1283,15 +1313,22 @@ __device__ inline void select_game(WaveLds &s, const DevCfg &c, const Tree &t, i
     const double sqrtNp = sqrt((double)Nn);
     double best = 0.0;
     int besti = -1, best_c0 = -1, best_nc = 0, best_N = 0, best_slot = -1, best_mv = 0xffff;
+    if constexpr (MULTI) m->best_vl = 0;
     for (int base = 0; base < nc; base += 64) {
       const int i = base + lane;
       double u = 0.0;
       bool valid = false;
       int Nc = 0, cc0 = -1, cnc = 0, cslot = -1, cmv = 0xffff;
+      if constexpr (MULTI) m->cvl = 0;
       if (i < nc) {
         Nc = t.N[nb + c0 + i];
         double Wc = t.W[nb + c0 + i];
         double Pc = (double)t.P[nb + c0 + i];
+        if constexpr (MULTI) {                     // N' = N + VL;  W' = W - vl*VL (strict) / W + vl*VL (PUCT: Q = -W/N)
+          m->cvl = m->lp.VL[nb + c0 + i];
+          Nc += m->cvl;
+          Wc = (c.rules & FPC_RULES_PUCT) ? Wc + m->lp.vl * (double)m->cvl : Wc - m->lp.vl * (double)m->cvl;
+        }
 #ifdef FPC_TREE_LDS_STAGE
         // A/B arm only (north_star: "per-game node N/W/P arrays staged in LDS"): the level's children pass through LDS
         // before the PUCT arithmetic reads them -- one more dependent round trip per level, no reuse to pay for it
@@ -1337,17 +1374,28 @@ __device__ inline void select_game(WaveLds &s, const DevCfg &c, const Tree &t, i
         idx = base + cur;
       }
       const int w_c0 = wave_read(cc0, cur), w_nc = wave_read(cnc, cur), w_N = wave_read(Nc, cur), w_slot = wave_read(cslot, cur), w_mv = wave_read(cmv, cur);
+      if constexpr (MULTI) {
+        const int w_vl = wave_read(m->cvl, cur);
+        if (idx != 0x7fffffff && (besti < 0 || ubest > best)) m->best_vl = w_vl;
+      }
       if (idx != 0x7fffffff && (besti < 0 || ubest > best)) { best = ubest; besti = idx; best_c0 = w_c0; best_nc = w_nc; best_N = w_N; best_slot = w_slot; best_mv = w_mv; }
     }
     if (besti < 0) { fail = true; break; }
     n = c0 + besti;
     c0 = best_c0; nc = best_nc; Nn = best_N;
     parent_slot = slot; slot = best_slot; leaf_mv = best_mv;
+    if constexpr (MULTI) m->leaf_vl = m->best_vl;
   }
   FPC_TS(5);
   if (fail) {                                // node.cpp:72-75 throws
-    if (lane == 0) { t.err[g] |= ERR_SELECT; t.alive[g] = 0; leaf_node[g] = -1; leaf_slot[g] = -1; }
+    if (lane == 0) { t.err[g] |= ERR_SELECT; t.alive[g] = 0; leaf_node[FPC_ROW] = -1; leaf_slot[FPC_ROW] = -1; }
     return;
+  }
+  if constexpr (MULTI) {
+    if (m->leaf_vl > 0) {                    // collision: a leaf already taken in this step; nothing is touched
+      if (lane == 0) { leaf_node[FPC_ROW] = -1; leaf_slot[FPC_ROW] = -1; }
+      return;
+    }
   }
   // ---- leaf state: the reference copies + MakeMoves a Board for every child at expansion time
   //      (node.cpp:90-91); here it is materialised the first time the node is reached.
@@ -1356,7 +1404,7 @@ __device__ inline void select_game(WaveLds &s, const DevCfg &c, const Tree &t, i
     lds_load_board(&s, &pool[parent_slot]);
     int from;
     const int to = flat_to(c, leaf_mv, &from);
-    const bool moved = make_move_wave(&s.b, from, to, c);
+    const bool moved = make_move_wave<MULTI>(&s.b, from, to, c);
     if (lane == 0) {
       int e = moved ? 0 : ERR_MOVE;
       int ns = nboards0;                     // fetched with the root's fields; only this block ever changes it
@@ -1368,7 +1416,7 @@ __device__ inline void select_game(WaveLds &s, const DevCfg &c, const Tree &t, i
     slot = s.first_legal;
     __syncthreads();
     if (slot < 0) {                          // board pool exhausted: the game leaves the search, nothing is overwritten
-      if (lane == 0) { t.alive[g] = 0; leaf_node[g] = -1; leaf_slot[g] = -1; }
+      if (lane == 0) { t.alive[g] = 0; leaf_node[FPC_ROW] = -1; leaf_slot[FPC_ROW] = -1; }
       return;
     }
   } else {
@@ -1377,7 +1425,7 @@ __device__ inline void select_game(WaveLds &s, const DevCfg &c, const Tree &t, i
   FPC_TS(6);
   // ---- GetGameResult (node.cpp:28-29) then, if in progress, GetLegalMoves
   //      (four_player_chess_board.py:38) on the same state, with their list reorderings
-  wave_position_ops(&s, c, true, true, -1);
+  wave_position_ops<MULTI>(&s, c, true, true, -1);
   FPC_TS(12);
   lds_store_board(&s, &t.boards[(size_t)g * t.board_cap + slot]);
   const int res = s.result;
@@ -1387,23 +1435,67 @@ __device__ inline void select_game(WaveLds &s, const DevCfg &c, const Tree &t, i
       backprop_lane0(t, nb, n, res == FPC_STALEMATE ? 0.0f : -1.0f);
       t.sims_done[g] += 1;
       t.alive[g] = 0;
-      leaf_node[g] = -1;
-      leaf_slot[g] = -1;
+      leaf_node[FPC_ROW] = -1;
+      leaf_slot[FPC_ROW] = -1;
     }
     return;
   }
   const int nl = s.nlegal;
-  uint16_t *lg = t.legal + (size_t)g * FPC_MAX_MOVES;
+  uint16_t *lg = t.legal + (size_t)FPC_ROW * FPC_MAX_MOVES;
   for (int k = lane; k < nl; k += 64) lg[k] = s.lsorted[k];
-  if (lane == 0) { leaf_node[g] = n; leaf_slot[g] = slot; leaf_turn[g] = s.b.turn; t.nlegal[g] = nl; t.path_len[g] = depth; }
+  if (lane == 0) {
+    leaf_node[FPC_ROW] = n; leaf_slot[FPC_ROW] = slot; leaf_turn[FPC_ROW] = s.b.turn;
+    t.nlegal[FPC_ROW] = nl; t.path_len[FPC_ROW] = depth;
+  }
+  if constexpr (MULTI) {                     // the row is pending: VL += 1 on every node of its path, root through leaf
+    __syncthreads();                         // lane 0's path stores are visible
+    const int len = depth < t.path_cap ? depth : t.path_cap;
+    for (int k = lane; k < len; k += 64) m->lp.VL[nb + path[k]] += 1;
+    if (lane == 0) leaf_slot[FPC_ROW] = g * t.board_cap + slot;
+    m->live = true;
+  }
   FPC_TS(13);
+#undef FPC_ROW
+}
+constexpr OneLeaf *ONE_LEAF = nullptr;
+
+// K descents of one game in one step (leaf-parallel search): row k*G + g for k = 0, 1, ...  The first row that is not
+// live (collision, terminal leaf, dead game) ends the game's selection for this step; its remaining rows are dead.
+__device__ inline void select_game_multi(WaveLds &s, const DevCfg &c, const Tree &t, int G, int g, int K, double Cpuct,
+                                         const double *logtab, bool to_next, const LeafPar &lp) {
+  int k = 0;
+  while (k < K) {
+    LeafRow r{lp, k, G, false, 0, 0, 0};
+    select_game(s, c, t, g, Cpuct, logtab, to_next, &r);
+    ++k;
+    if (!r.live) break;
+    __syncthreads();                         // this descent's tree stores (VL, bslot, nboards, board) precede the next one
+  }
+  int *const leaf_node = to_next ? t.leaf_node_nx : t.leaf_node;
+  int *const leaf_slot = to_next ? t.leaf_slot_nx : t.leaf_slot;
+  if (lane_id() == 0)
+    for (; k < K; ++k) { leaf_node[k * G + g] = -1; leaf_slot[k * G + g] = -1; }
 }
 
 __global__ void __launch_bounds__(64) k_select(DevCfg c, Tree t, int G, double Cpuct, const double *logtab) {
   __shared__ WaveLds s;
   const int g = blockIdx.x;
   if (g >= G) return;
-  select_game(s, c, t, g, Cpuct, logtab, false);
+  select_game(s, c, t, g, Cpuct, logtab, false, ONE_LEAF);
+}
+
+__global__ void __launch_bounds__(64) k_select_multi(DevCfg c, Tree t, int G, int K, double Cpuct, const double *logtab, LeafPar lp) {
+  __shared__ WaveLds s;
+  const int g = blockIdx.x;
+  if (g >= G) return;
+  select_game_multi(s, c, t, G, g, K, Cpuct, logtab, false, lp);
+}
+
+// pending-visit counters of the roots (node storage, and with it VL, is reused across searches; children are zeroed
+// where they are created)
+__global__ void __launch_bounds__(64) k_vl_roots(int *VL, int node_cap, int G) {
+  const int g = blockIdx.x * 64 + lane_id();
+  if (g < G) VL[(size_t)g * node_cap] = 0;
 }
 
 // ================================================================================================
@@ -1447,16 +1539,20 @@ struct ExpandPre {     // what expand_game / expand_legal_game fetch up front fo
   float v;             // value[g]
   int path_len, path_node, nnodes;
 };
-__device__ __forceinline__ ExpandPre expand_prefetch(const Tree &t, int g, const float *value) {
+__device__ __forceinline__ ExpandPre expand_prefetch(const Tree &t, int g, int row, const float *value) {
   ExpandPre e;
   const int lane = lane_id();
-  e.v = value[g];
-  e.path_len = t.path_len[g];
-  e.path_node = lane < t.path_cap ? t.path[(size_t)g * t.path_cap + lane] : 0;
+  e.v = value[row];
+  e.path_len = t.path_len[row];
+  e.path_node = lane < t.path_cap ? t.path[(size_t)row * t.path_cap + lane] : 0;
   e.nnodes = t.nnodes[g];
   return e;
 }
-__device__ __forceinline__ void expand_finish(WaveLds &s, const Tree &t, int g, size_t nb, int n, int nl, bool nan, const ExpandPre &pre) {
+// MULTI (leaf-parallel): `row` is the leaf's row (k*G + g); the backup also takes the row's pending visit off its path
+// (VL -= 1) and the new children start with VL = 0.  Returns false on a policy error.
+template <bool MULTI>
+__device__ __forceinline__ bool expand_finish(WaveLds &s, const Tree &t, int g, int row, size_t nb, int n, int nl, bool nan, const ExpandPre &pre,
+                                              int *VL) {
   const int lane = lane_id();
   if (lane == 0) {
     float T = 0.f;
@@ -1467,7 +1563,7 @@ __device__ __forceinline__ void expand_finish(WaveLds &s, const Tree &t, int g, 
   __syncthreads();
   if (s.errbits) {                          // the reference would expand all A indices and throw
     if (lane == 0) { t.err[g] |= ERR_POLICY; t.alive[g] = 0; }
-    return;
+    return false;
   }
   const float T = s.scal_f;
   // root Dirichlet noise (N4): prior' = (1 - eps) prior + eps g_j / sum g over the root's legal moves,
@@ -1486,7 +1582,11 @@ __device__ __forceinline__ void expand_finish(WaveLds &s, const Tree &t, int g, 
   const float SG = s.scal_f;
   const bool add_noise = noisy && SG > 0.f;      // rows without positive mass (never uploaded, all-zero draws) leave the priors alone
   // BackpropagateNodes (mcts.py:78) before ExpandNodes (mcts.py:79)
-  backprop_path(t, nb, g, pre.v, pre.path_len, pre.path_node);
+  backprop_path(t, nb, row, pre.v, pre.path_len, pre.path_node);
+  if constexpr (MULTI) {
+    const int *path = t.path + (size_t)row * t.path_cap;
+    for (int k = lane; k < pre.path_len; k += 64) VL[nb + (k < 64 ? pre.path_node : path[k])] -= 1;
+  }
   if (lane == 0) t.sims_done[g] += 1;
   // children: ascending flat order, entries with prior == 0 dropped (torch.nonzero, mcts.py:84)
   const int base_node = pre.nnodes;
@@ -1506,6 +1606,7 @@ __device__ __forceinline__ void expand_finish(WaveLds &s, const Tree &t, int g, 
       if (k < t.node_cap) {
         t.N[nb + k] = 1; t.W[nb + k] = 0.0; t.P[nb + k] = pr; t.mv[nb + k] = s.lsorted[j];
         t.parent[nb + k] = n; t.child0[nb + k] = -1; t.nch[nb + k] = 0; t.bslot[nb + k] = -1;
+        if constexpr (MULTI) VL[nb + k] = 0;
       }
     }
     created += __popcll(bal);
@@ -1516,6 +1617,7 @@ __device__ __forceinline__ void expand_finish(WaveLds &s, const Tree &t, int g, 
       t.child0[nb + n] = base_node; t.nch[nb + n] = (uint16_t)created; t.nnodes[g] = base_node + created;
     }
   }
+  return true;
 }
 
 // ================================================================================================
@@ -1606,33 +1708,35 @@ __device__ __forceinline__ float logit_at(const LogitSrc &L, int g, int A, int i
   for (int k = 0; k < LOGIT_MAX_SLABS; ++k) v = k < cnt ? v + p[k] : v;
   return v;
 }
-__device__ inline void expand_game(WaveLds &s, const DevCfg &c, const Tree &t, int G, int g, const LogitSrc &logits, const float *stats,
-                                   const float *value) {
+// G: rows of the step (games when one leaf per game); g the game, row the leaf's row (== g unless MULTI)
+template <bool MULTI>
+__device__ inline bool expand_game_t(WaveLds &s, const DevCfg &c, const Tree &t, int G, int g, int row, const LogitSrc &logits,
+                                     const float *stats, const float *value, int *VL) {
   const int lane = lane_id();
   const size_t nb = (size_t)g * t.node_cap;
   const int nchunks = (c.A / 4 + SM_THREADS - 1) / SM_THREADS;     // A = (8R+8)*R*R is a multiple of 4 for even R
-  const float *st = stats + (size_t)g * SM_MAXCH * SM_REC;
-  const uint16_t *legal = t.legal + (size_t)g * FPC_MAX_MOVES;
+  const float *st = stats + (size_t)row * SM_MAXCH * SM_REC;
+  const uint16_t *legal = t.legal + (size_t)row * FPC_MAX_MOVES;
   // ONE round trip for everything whose address depends on no other load (a lone wave per CU pays the full memory
   // latency per dependent load): the leaf, its legal list (first 64 entries), the chunk records, the leaf turns of the
   // first 64 games (the batch's first live leaf is almost always among them), value / path / node count.
-  const int n = t.leaf_node[g];
-  const int nl = t.nlegal[g];
-  const int own_turn = t.leaf_turn[g];
+  const int n = t.leaf_node[row];
+  const int nl = t.nlegal[row];
+  const int own_turn = t.leaf_turn[row];
   const int scan_node = lane < G ? t.leaf_node[lane] : -1;
   const int scan_turn = lane < G ? t.leaf_turn[lane] : 0;
   const int fl0 = legal[lane];                                    // lane < 64 <= FPC_MAX_MOVES: always in bounds
   float mc = -__builtin_inff(), sc = 0.f;
   bool nan = false;
   if (lane < nchunks) { mc = st[lane * SM_REC]; sc = st[lane * SM_REC + 1]; nan = st[lane * SM_REC + 2] != 0.f; }
-  const ExpandPre pre = expand_prefetch(t, g, value);
+  const ExpandPre pre = expand_prefetch(t, g, row, value);
   int turn0;
   if (c.rules & FPC_RULES_ROTATION) turn0 = own_turn;
   else {                                                          // the batch's FIRST live leaf (Q6)
     const unsigned long long bal = __ballot(scan_node >= 0);
     turn0 = bal ? wave_read(scan_turn, (int)__ffsll((long long)bal) - 1) : (G > 64 ? first_leaf_turn(t.leaf_node, t.leaf_turn, G) : 0);
   }
-  if (n < 0) return;
+  if (n < 0) return true;
   FPC_TS(1);
   float m = mc;
   for (int off = 32; off >= 1; off >>= 1) { const float o = __shfl_xor(m, off); m = o > m ? o : m; }
@@ -1646,12 +1750,16 @@ __device__ inline void expand_game(WaveLds &s, const DevCfg &c, const Tree &t, i
     const int fl = j < 64 ? fl0 : (int)legal[j];
     const int plane = fl / c.RR, pos = fl % c.RR;
     const int src = plane * c.RR + rot90_src(c.R, -turn0, pos / c.R, pos % c.R);
-    s.pri[j] = fpc_expf(logit_at(logits, g, c.A, src) - m) * inv;
+    s.pri[j] = fpc_expf(logit_at(logits, row, c.A, src) - m) * inv;
     s.lsorted[j] = (uint16_t)fl;
   }
   __syncthreads();
   FPC_TS(3);
-  expand_finish(s, t, g, nb, n, nl, nan, pre);
+  return expand_finish<MULTI>(s, t, g, row, nb, n, nl, nan, pre, VL);
+}
+__device__ __forceinline__ void expand_game(WaveLds &s, const DevCfg &c, const Tree &t, int G, int g, const LogitSrc &logits, const float *stats,
+                                            const float *value) {
+  (void)expand_game_t<false>(s, c, t, G, g, g, logits, stats, value, nullptr);
 }
 
 __global__ void __launch_bounds__(EXPAND_THREADS) k_expand(DevCfg c, Tree t, int G, LogitSrc logits, const float *stats, const float *value) {
@@ -1674,7 +1782,7 @@ __global__ void __launch_bounds__(EXPAND_THREADS) k_expand_select(DevCfg c, Tree
   expand_game(s, c, t, G, g, logits, stats, value);
   __syncthreads();                           // the new children (global stores of other lanes) are visible to the descent
   FPC_TS(4);
-  select_game(s, c, t, g, Cpuct, logtab, true);
+  select_game(s, c, t, g, Cpuct, logtab, true, ONE_LEAF);
 }
 
 
@@ -1688,15 +1796,16 @@ __global__ void __launch_bounds__(EXPAND_THREADS) k_expand_select(DevCfg c, Tree
 // maximum, which the full softmax would flush to zero (child dropped / policy error) and this form
 // cannot see.  One wave per game.
 // ================================================================================================
-__device__ inline void expand_legal_game(WaveLds &s, const DevCfg &c, const Tree &t, int g, const float *ll, const float *value) {
+template <bool MULTI>
+__device__ inline bool expand_legal_game_t(WaveLds &s, const DevCfg &c, const Tree &t, int g, int row, const float *ll, const float *value, int *VL) {
   const int lane = lane_id();
-  const int n = t.leaf_node[g];
-  const ExpandPre pre = expand_prefetch(t, g, value);
-  if (n < 0) return;
+  const int n = t.leaf_node[row];
+  const ExpandPre pre = expand_prefetch(t, g, row, value);
+  if (n < 0) return true;
   const size_t nb = (size_t)g * t.node_cap;
-  const int nl = t.nlegal[g];
-  const uint16_t *legal = t.legal + (size_t)g * FPC_MAX_MOVES;
-  const float *lg = ll + (size_t)g * FPC_MAX_MOVES;
+  const int nl = t.nlegal[row];
+  const uint16_t *legal = t.legal + (size_t)row * FPC_MAX_MOVES;
+  const float *lg = ll + (size_t)row * FPC_MAX_MOVES;
   float m = -__builtin_inff();
   bool nan = false;
   for (int j = lane; j < nl; j += 64) { const float v = lg[j]; nan |= v != v; m = v > m ? v : m; }
@@ -1707,7 +1816,10 @@ __device__ inline void expand_legal_game(WaveLds &s, const DevCfg &c, const Tree
     s.lsorted[j] = legal[j];
   }
   __syncthreads();
-  expand_finish(s, t, g, nb, n, nl, nan, pre);
+  return expand_finish<MULTI>(s, t, g, row, nb, n, nl, nan, pre, VL);
+}
+__device__ __forceinline__ void expand_legal_game(WaveLds &s, const DevCfg &c, const Tree &t, int g, const float *ll, const float *value) {
+  (void)expand_legal_game_t<false>(s, c, t, g, g, ll, value, nullptr);
 }
 
 __global__ void __launch_bounds__(64) k_expand_legal(DevCfg c, Tree t, int G, const float *ll, const float *value) {
@@ -1725,7 +1837,60 @@ __global__ void __launch_bounds__(64) k_expand_legal_select(DevCfg c, Tree t, in
   if (g >= G) return;
   expand_legal_game(s, c, t, g, ll, value);
   __syncthreads();
-  select_game(s, c, t, g, Cpuct, logtab, true);
+  select_game(s, c, t, g, Cpuct, logtab, true, ONE_LEAF);
+}
+
+// ================================================================================================
+// Leaf-parallel search (fpc_search_set_leaves): the expansion of a step of `kexp` leaves per game, one block per game
+// walking the game's live rows k*G + g in ascending k (that order fixes the f64 sums of the backups), each with the
+// arithmetic of k_expand / k_expand_legal from ITS row's logits, statistics and value; the _select twins then select the
+// next step's `ksel` leaves of the game (rows written to the _nx leaf arrays, as k_expand_select does).
+// ================================================================================================
+template <bool LEGAL>
+__device__ inline void expand_game_multi(WaveLds &s, const DevCfg &c, const Tree &t, int G, int g, int kexp, const LogitSrc &logits,
+                                         const float *ll, const float *stats, const float *value, int *VL) {
+  for (int k = 0; k < kexp; ++k) {
+    const int row = k * G + g;
+    bool ok;
+    if constexpr (LEGAL) ok = expand_legal_game_t<true>(s, c, t, g, row, ll, value, VL);
+    else ok = expand_game_t<true>(s, c, t, kexp * G, g, row, logits, stats, value, VL);
+    __syncthreads();                         // this row's tree stores (N, W, VL, children, nnodes) precede the next row
+    if (!ok) break;                          // policy error: the game has left the search
+  }
+}
+
+__global__ void __launch_bounds__(EXPAND_THREADS) k_expand_multi(DevCfg c, Tree t, int G, int kexp, LogitSrc logits, const float *stats,
+                                                                 const float *value, LeafPar lp) {
+  __shared__ WaveLds s;
+  const int g = blockIdx.x;
+  if (g >= G) return;
+  expand_game_multi<false>(s, c, t, G, g, kexp, logits, nullptr, stats, value, lp.VL);
+}
+
+__global__ void __launch_bounds__(EXPAND_THREADS) k_expand_select_multi(DevCfg c, Tree t, int G, int kexp, int ksel, LogitSrc logits,
+                                                                        const float *stats, const float *value, double Cpuct,
+                                                                        const double *logtab, LeafPar lp) {
+  __shared__ WaveLds s;
+  const int g = blockIdx.x;
+  if (g >= G) return;
+  expand_game_multi<false>(s, c, t, G, g, kexp, logits, nullptr, stats, value, lp.VL);
+  select_game_multi(s, c, t, G, g, ksel, Cpuct, logtab, true, lp);
+}
+
+__global__ void __launch_bounds__(64) k_expand_legal_multi(DevCfg c, Tree t, int G, int kexp, const float *ll, const float *value, LeafPar lp) {
+  __shared__ WaveLds s;
+  const int g = blockIdx.x;
+  if (g >= G) return;
+  expand_game_multi<true>(s, c, t, G, g, kexp, LogitSrc{}, ll, nullptr, value, lp.VL);
+}
+
+__global__ void __launch_bounds__(64) k_expand_legal_select_multi(DevCfg c, Tree t, int G, int kexp, int ksel, const float *ll,
+                                                                  const float *value, double Cpuct, const double *logtab, LeafPar lp) {
+  __shared__ WaveLds s;
+  const int g = blockIdx.x;
+  if (g >= G) return;
+  expand_game_multi<true>(s, c, t, G, g, kexp, LogitSrc{}, ll, nullptr, value, lp.VL);
+  select_game_multi(s, c, t, G, g, ksel, Cpuct, logtab, true, lp);
 }
 
 }  // namespace fpc

@@ -14,6 +14,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FPC_ENGINE_LIB") or os.path.join(HERE, "csrc", "libfpc_engine.so")
 
 MAX_SQ, MAX_PL, NO_SQ, MAX_MOVES = 196, 16, 255, 256
+MAX_LEAVES = 8                          # FPC_MAX_LEAVES: leaves per game per step of a leaf-parallel search
 RULES_STRICT, RULES_PUCT, RULES_ROTATION, RULES_PLANES, RULES_FULL_MOVES, RULES_FIXED = 0, 1, 2, 4, 8, 15
 
 
@@ -130,6 +131,7 @@ _SIGS = {
     "fpc_stream": (C.c_void_p, [C.c_void_p]),
     "fpc_set_rules": (C.c_int, [C.c_void_p, C.c_int]),
     "fpc_search_set_root_noise": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_float]),
+    "fpc_search_set_leaves": (C.c_int, [C.c_void_p, C.c_int, C.c_double]),
     "fpc_tuples_reserve": (C.c_int, [C.c_void_p, C.c_int]),
     "fpc_tuples_reset": (C.c_int, [C.c_void_p]),
     "fpc_collect_tuples": (C.c_int, [C.c_void_p, P(C.c_int), C.c_int]),
@@ -418,6 +420,11 @@ class Engine:
     def set_rules(self, rules):
         """0 = strict reference semantics (default); RULES_FIXED = all corrections"""
         self._chk(self.L.fpc_set_rules(self.h, int(rules)))
+
+    def set_leaves(self, k, virtual_loss=1.0):
+        """leaf-parallel search (include/fpc_engine.h fpc_search_set_leaves): up to k leaves per game per simulation
+        step, kept apart by virtual loss; the step-wise evaluator then sees [k*G, 24, R, R].  k = 1: one leaf per game."""
+        self._chk(self.L.fpc_search_set_leaves(self.h, int(k), float(virtual_loss)))
 
     def set_root_noise(self, gamma, eps):
         """gamma: float32 array [n_games, MAX_MOVES] of Gamma(alpha) draws (None: off)"""

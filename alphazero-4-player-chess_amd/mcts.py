@@ -12,7 +12,14 @@ by the engine:
   callable sees the encoded leaves `[G,24,R,R]` and returns `(logits [G,A], value [G,1])`.
   Difference from the reference: the batch always has one slot per game (finished games are
   all-zero rows whose outputs are ignored) instead of only the live leaves.
+
+Leaf-parallel search (opt-in, not reference semantics; include/fpc_engine.h fpc_search_set_leaves):
+args["leaves_per_step"] = K > 1 selects up to K leaves per game per simulation step, kept apart by
+args["virtual_loss"] (default 1.0); the engine then has K*G rows and the evaluator sees [K*G,24,R,R]
+(row k*G + g = the k-th leaf of game g), num_searches leaves in ceil(num_searches / K) steps.
 """
+import math
+
 import numpy as np
 import torch
 
@@ -53,6 +60,12 @@ class MCTS:
         self.rules = {"strict": 0, "fixed": 15}.get(rules, rules)
         self.root_noise = bool(args.get("root_noise", False)) if hasattr(args, "get") else False
         self._noise_rng = np.random.default_rng(int(args.get("noise_seed", 0))) if self.root_noise else None
+        self.leaves = int(args.get("leaves_per_step", 1)) if hasattr(args, "get") else 1
+        self.virtual_loss = float(args.get("virtual_loss", 1.0)) if hasattr(args, "get") else 1.0
+
+    def engine_rows(self, G):
+        """rows of the engine handle a search of G games needs (G * leaves_per_step)"""
+        return G * self.leaves
 
     def sync_weights(self, eng):
         """(re-)export the network into the engine when its parameters changed (optimizer.step)."""
@@ -77,9 +90,10 @@ class MCTS:
     def search(self, games):
         G = len(games)
         sims = int(self.args["num_searches"])
-        eng = az.engine(G, sims, self.nn_dtype if self._native else None)
+        eng = az.engine(self.engine_rows(G), sims, self.nn_dtype if self._native else None)
         pods = [g._b for g in games]
         eng.set_rules(int(self.rules))
+        eng.set_leaves(self.leaves, self.virtual_loss)     # the handle is process-wide: set on every search
         if self.root_noise:
             import fpc_ffi
             gamma = self._noise_rng.standard_gamma(float(self.args["dirichlet_alpha"]), size=(G, fpc_ffi.MAX_MOVES)).astype(np.float32)
@@ -112,34 +126,52 @@ class MCTS:
         host_engine = not torch.cuda.is_available()    # only true for the test-suite's emulator build
         R, A = eng.R, eng.A
         keep = None
+        # leaf-parallel: ceil(sims / K) steps of K leaves per game, the last one of the remainder (set before the
+        # selection of that step, which the preceding expand_select performs)
+        K = self.leaves
+        steps = math.ceil(sims / K)
+        last_k = sims - K * (steps - 1)
+
+        def leaves_of(step):
+            return K if step + 1 < steps else last_k
+
+        rows = G * leaves_of(0)
+        if steps > 0 and leaves_of(0) != K:
+            eng.set_leaves(leaves_of(0), self.virtual_loss)
         # mcts.py:36-38: select -> evaluate -> expand per simulation; between two evaluations the expansion and the
         # next selection are one launch (fpc_search_expand_select)
-        n_live, enc_ptr = eng.search_select() if sims > 0 else (0, None)
-        for i in range(sims):
-            last = i == sims - 1
+        n_live, enc_ptr = eng.search_select() if steps > 0 else (0, None)
+        for i in range(steps):
+            last = i == steps - 1
+            if not last and leaves_of(i + 1) != leaves_of(i):
+                eng.set_leaves(leaves_of(i + 1), self.virtual_loss)
             if n_live == 0:
                 if not last:
                     n_live, enc_ptr = eng.search_select()
+                    rows = G * leaves_of(i + 1)
                 continue
             if host_engine:
                 import ctypes
                 import numpy as np
                 enc = torch.from_numpy(np.ctypeslib.as_array(ctypes.cast(enc_ptr, ctypes.POINTER(ctypes.c_float)),
-                                                             shape=(G, 24, R, R)).copy())
+                                                             shape=(rows, 24, R, R)).copy())
                 logits, value = self.neural_net(enc)
-                logits = logits.to(torch.float32).contiguous().view(G, A)
-                value = value.to(torch.float32).contiguous().view(G)
+                logits = logits.to(torch.float32).contiguous().view(rows, A)
+                value = value.to(torch.float32).contiguous().view(rows)
             else:
-                enc = torch.as_tensor(_DevPtr(enc_ptr, (G, 24, R, R)), device="cuda")
+                enc = torch.as_tensor(_DevPtr(enc_ptr, (rows, 24, R, R)), device="cuda")
                 logits, value = self.neural_net(enc if on_gpu else enc.cpu())
-                logits = logits.to(device="cuda", dtype=torch.float32).contiguous().view(G, A)
-                value = value.to(device="cuda", dtype=torch.float32).contiguous().view(G)
+                logits = logits.to(device="cuda", dtype=torch.float32).contiguous().view(rows, A)
+                value = value.to(device="cuda", dtype=torch.float32).contiguous().view(rows)
                 torch.cuda.synchronize()
             keep = (logits, value)
             if last:
                 eng.search_expand(logits.data_ptr(), value.data_ptr())
             else:
                 n_live, enc_ptr = eng.search_expand_select(logits.data_ptr(), value.data_ptr())
+                rows = G * leaves_of(i + 1)
             if not host_engine:
                 torch.cuda.synchronize()
         del keep
+        if last_k != K:
+            eng.set_leaves(K, self.virtual_loss)

@@ -173,6 +173,19 @@ int fpc_set_rules(fpc_engine *e, int rules);
  * gamma: host array [n_games][FPC_MAX_MOVES] of Gamma(alpha, 1) draws made (and seeded) by the caller;
  * NULL switches the noise off. */
 int fpc_search_set_root_noise(fpc_engine *e, const float *gamma, int n_games, float eps);
+/* ---- leaf-parallel search (opt-in, held against a model of these semantics, not against the reference) ----------
+ * Each simulation step selects up to `leaves` = K leaves per game instead of one, kept apart by virtual loss, so the
+ * network sees up to K*G rows.  Row r = k*G + g holds the k-th leaf game g selected in this step (K = 1: today's
+ * layout, today's kernels).  The descent sees N' = N + VL and W' = W - vl*VL (strict) / W + vl*VL (FPC_RULES_PUCT),
+ * VL = pending visits of the step; a descent that ends on a pending leaf (a collision) or on a terminal leaf ends the
+ * game's selection for the step.  Expansion walks a game's live rows in ascending k.  fpc_search_run(sims) runs
+ * ceil(sims/K) steps, the last of the remainder; every leaf counts against max_sims.
+ * Persistent; may be changed between the steps of a running search (it applies to the NEXT selection).  Step-wise
+ * callers: *n_live counts live rows, enc_dev is [K*G,24,R,R], logits_dev / value_dev have K*G rows.
+ * FPC_EINVAL: leaves outside 1..FPC_MAX_LEAVES, virtual_loss negative or not finite, K*G > max_games (rows must fit:
+ * checked here during a running search, at fpc_search_begin, and by every call that selects leaves). */
+#define FPC_MAX_LEAVES 8
+int fpc_search_set_leaves(fpc_engine *e, int leaves, double virtual_loss);
 
 /* Root read-back == what alphazero.py:104-110 reads through Node.GetChildren /
  * GetMoveMade().GetFlatIndex() / GetVisitCount().  Arrays are [n_games][max_children].
