@@ -471,16 +471,31 @@ int fpc_boards_legal_mask(fpc_engine *e, fpc_board *boards, int n, float *out_ho
 }
 
 // ------------------------------------------------------------------------------------------------
+// Search.  A simulation step selects a leaf (or K leaves, fpc_search_set_leaves) per game, stages them for the network,
+// evaluates them and expands them; for all but the last step of a call the expansion and the NEXT step's selection are
+// one launch (k_expand(_legal)_select(_multi)), so a step is 4 dependent kernels instead of 5.  fpc_search_run drives
+// that sequence with the internal network; the step entry points (fpc_search_select / _expand_select / _expand) drive
+// it for an external evaluator.  Both go through the same helpers: admit (the checks and the max_sims accounting of a
+// call that selects), launch_select, stage_leaves (fpc_search_run) or finish_select (step entry points), and
+// launch_expand, which picks the expansion kernel.  The selection waiting to be expanded is described by rows_k and
+// pending_vl; only launch_select and launch_expand change them.
+
+// every call that selects checks that the rows fit (the setting may have changed after fpc_search_results)
+static int check_rows(fpc_engine *e, int leaves, int G) {
+  if ((long)leaves * G > e->cfg.max_games)
+    return fail(e, FPC_EINVAL, "%d leaves x %d games = %ld rows > max_games %d (fpc_search_set_leaves)", leaves, G,
+                (long)leaves * G, e->cfg.max_games);
+  return 0;
+}
+
 int fpc_search_begin(fpc_engine *e, const fpc_board *roots, int n_games, double c_puct) {
   if (!e || !roots || n_games < 1) return fail(e, FPC_EINVAL, "bad argument");
   USE_DEV(e);
   if (n_games > e->cfg.max_games) return fail(e, FPC_EINVAL, "n_games %d > max_games %d", n_games, e->cfg.max_games);
-  if ((long)e->leaves * n_games > e->cfg.max_games)
-    return fail(e, FPC_EINVAL, "%d leaves x %d games = %ld rows > max_games %d (fpc_search_set_leaves)", e->leaves, n_games,
-                (long)e->leaves * n_games, e->cfg.max_games);
+  int r;
+  if ((r = check_rows(e, e->leaves, n_games))) return r;
   if (e->t.noise && e->noise_n != n_games)
     return fail(e, FPC_EINVAL, "root noise was uploaded for %d games, this search has %d: call fpc_search_set_root_noise again (or with NULL)", e->noise_n, n_games);
-  int r;
   if ((r = check_boards(e, roots, n_games))) return r;
   e->G = n_games;
   e->Cpuct = c_puct;
@@ -500,31 +515,30 @@ int fpc_search_begin(fpc_engine *e, const fpc_board *roots, int n_games, double 
   return 0;
 }
 
+static int check_searching(fpc_engine *e) {
+  return !e || !e->searching ? fail(e, FPC_ESTATE, "fpc_search_begin has not been called") : 0;
+}
+
+// admission of a call that selects, after its own argument checks: the rows of the engine's leaves per game fit, and
+// n more simulations stay within max_sims (pools + log table), which they are then counted against
+static int admit(fpc_engine *e, int n) {
+  int r;
+  if ((r = check_rows(e, e->leaves, e->G))) return r;
+  if (e->sims_issued + n > e->cfg.max_sims) return fail(e, FPC_ECAPACITY, "more than max_sims = %d simulations since fpc_search_begin", e->cfg.max_sims);
+  e->sims_issued += n;
+  return 0;
+}
+
 static LeafPar leafpar(const fpc_engine *e) { return LeafPar{e->d_VL, e->vl}; }
 
-// every call that selects leaves checks that the rows fit (the setting may have changed after fpc_search_results)
-static int check_rows(fpc_engine *e) {
-  if ((long)e->leaves * e->G > e->cfg.max_games)
-    return fail(e, FPC_EINVAL, "%d leaves x %d games = %ld rows > max_games %d (fpc_search_set_leaves)", e->leaves, e->G,
-                (long)e->leaves * e->G, e->cfg.max_games);
-  return 0;
-}
-
-static int launch_select(fpc_engine *e) {
-  mark(e, 0);
+// k leaves per game (k_select_multi), or one (k_select) in a one-leaf search
+static void launch_select(fpc_engine *e, int k) {
   if (e->multi)
-    FPC_LAUNCH(k_select_multi, e->G, 64, e->stream, e->dc, e->t, e->G, e->leaves, e->Cpuct, (const double *)e->d_logtab, leafpar(e));
+    FPC_LAUNCH(k_select_multi, e->G, 64, e->stream, e->dc, e->t, e->G, k, e->Cpuct, (const double *)e->d_logtab, leafpar(e));
   else
     FPC_LAUNCH(k_select, e->G, 64, e->stream, e->dc, e->t, e->G, e->Cpuct, (const double *)e->d_logtab);
-  e->rows_k = e->multi ? e->leaves : 1;
+  e->rows_k = k;
   e->pending_vl = e->multi;
-  return 0;
-}
-
-// softmax chunk statistics of logits that did not come from the internal policy Linear (one record set per row)
-static void launch_partials(fpc_engine *e, const float *logits_dev) {
-  const int nchunks = (e->dc.A / 4 + SM_THREADS - 1) / SM_THREADS, rows = e->rows_k * e->G;
-  FPC_LAUNCH(k_softmax_partials, rows * nchunks, SM_THREADS, e->stream, logits_dev, e->dc.A, rows, nchunks, e->d_stats);
 }
 
 // after a k_expand_select launch the leaves it selected become the current ones
@@ -534,9 +548,49 @@ static void swap_leaf_arrays(fpc_engine *e) {
   std::swap(e->t.leaf_turn, e->t.leaf_turn_nx);
 }
 
-// the leaf-parallel kernels leave the GLOBAL pool index g*board_cap + slot in leaf_slot: the encoders read it with stride 0
-static int leaf_board_stride(const fpc_engine *e) { return e->multi ? 0 : e->t.board_cap; }
+// The expansion of the pending selection from the full head's logits (src + softmax chunk statistics) or, with `legal`
+// set, from the legal-only head's; with ksel > 0 fused with the selection of the next step's ksel leaves per game.
+// A one-leaf selection made before fpc_search_set_leaves switched the search to leaf-parallel holds no pending visit:
+// it is expanded by the one-leaf kernel, and the next step's leaves are selected by k_select_multi.
+static void launch_expand(fpc_engine *e, const LogitSrc &src, const float *stats, const float *legal, const float *value, int ksel) {
+  const int G = e->G, kexp = e->rows_k;
+  const bool fuse = ksel > 0, fused = fuse && e->pending_vl == e->multi;    // one launch expands and selects
+  const double *logtab = e->d_logtab;
+  if (e->pending_vl) {
+    if (legal && fuse)
+      FPC_LAUNCH(k_expand_legal_select_multi, G, 64, e->stream, e->dc, e->t, G, kexp, ksel, legal, value, e->Cpuct, logtab, leafpar(e));
+    else if (legal)
+      FPC_LAUNCH(k_expand_legal_multi, G, 64, e->stream, e->dc, e->t, G, kexp, legal, value, leafpar(e));
+    else if (fuse)
+      FPC_LAUNCH(k_expand_select_multi, G, EXPAND_THREADS, e->stream, e->dc, e->t, G, kexp, ksel, src, stats, value, e->Cpuct, logtab, leafpar(e));
+    else
+      FPC_LAUNCH(k_expand_multi, G, EXPAND_THREADS, e->stream, e->dc, e->t, G, kexp, src, stats, value, leafpar(e));
+  } else {
+    if (legal && fused)
+      FPC_LAUNCH(k_expand_legal_select, G, 64, e->stream, e->dc, e->t, G, legal, value, e->Cpuct, logtab);
+    else if (legal)
+      FPC_LAUNCH(k_expand_legal, G, 64, e->stream, e->dc, e->t, G, legal, value);
+    else if (fused)
+      FPC_LAUNCH(k_expand_select, G, EXPAND_THREADS, e->stream, e->dc, e->t, G, src, stats, value, e->Cpuct, logtab);
+    else
+      FPC_LAUNCH(k_expand, G, EXPAND_THREADS, e->stream, e->dc, e->t, G, src, stats, value);
+  }
+  if (fused) swap_leaf_arrays(e);
+  else if (fuse) launch_select(e, ksel);
+  e->rows_k = fuse ? ksel : 1;
+  e->pending_vl = fuse && e->multi;
+}
 
+// softmax chunk statistics of logits that did not come from the internal policy Linear (one record set per row)
+static void launch_partials(fpc_engine *e, const float *logits_dev) {
+  const int nchunks = (e->dc.A / 4 + SM_THREADS - 1) / SM_THREADS, rows = e->rows_k * e->G;
+  FPC_LAUNCH(k_softmax_partials, rows * nchunks, SM_THREADS, e->stream, logits_dev, e->dc.A, rows, nchunks, e->d_stats);
+}
+
+// the leaf-parallel kernels leave the GLOBAL pool index g*board_cap + slot in leaf_slot: the encoders read it with stride 0
+static int leaf_board_stride(const fpc_engine *e) { return e->pending_vl ? 0 : e->t.board_cap; }
+
+// the step entry points: the pending leaves encoded in f32 for the external evaluator, and how many are live
 static int finish_select(fpc_engine *e, int *n_live, const float **enc_dev) {
   const int rows = e->rows_k * e->G;
   FPC_LAUNCH(k_encode, rows, 64, e->stream, e->dc, (const fpc_board *)e->t.boards, leaf_board_stride(e),
@@ -556,44 +610,25 @@ static int finish_select(fpc_engine *e, int *n_live, const float **enc_dev) {
 }
 
 int fpc_search_select(fpc_engine *e, int *n_live, const float **enc_dev) {
-  if (!e || !e->searching) return fail(e, FPC_ESTATE, "fpc_search_begin has not been called");
-  USE_DEV(e);
   int r;
-  if ((r = check_rows(e))) return r;
-  if (e->sims_issued + e->leaves > e->cfg.max_sims) return fail(e, FPC_ECAPACITY, "more than max_sims = %d simulations since fpc_search_begin", e->cfg.max_sims);
-  e->sims_issued += e->leaves;
-  launch_select(e);
+  if ((r = check_searching(e))) return r;
+  USE_DEV(e);
+  if ((r = admit(e, e->leaves))) return r;
+  mark(e, 0);
+  launch_select(e, e->leaves);
   return finish_select(e, n_live, enc_dev);
 }
 
 int fpc_search_expand_select(fpc_engine *e, const float *logits_dev, const float *value_dev, int *n_live, const float **enc_dev) {
-  if (!e || !e->searching) return fail(e, FPC_ESTATE, "fpc_search_begin has not been called");
+  int r;
+  if ((r = check_searching(e))) return r;
   USE_DEV(e);
   if (!logits_dev || !value_dev) return fail(e, FPC_EINVAL, "null logits/value");
-  int r;
-  if ((r = check_rows(e))) return r;
-  if (e->sims_issued + e->leaves > e->cfg.max_sims) return fail(e, FPC_ECAPACITY, "more than max_sims = %d simulations since fpc_search_begin", e->cfg.max_sims);
-  e->sims_issued += e->leaves;
+  if ((r = admit(e, e->leaves))) return r;
   mark(e, 3);
   launch_partials(e, logits_dev);
-  const LogitSrc src{logits_dev, nullptr, nullptr, 0, 0, 0, 0, 256};
-  if (e->pending_vl) {
-    FPC_LAUNCH(k_expand_select_multi, e->G, EXPAND_THREADS, e->stream, e->dc, e->t, e->G, e->rows_k, e->leaves, src, (const float *)e->d_stats,
-               value_dev, e->Cpuct, (const double *)e->d_logtab, leafpar(e));
-    swap_leaf_arrays(e);
-  } else if (!e->multi) {
-    FPC_LAUNCH(k_expand_select, e->G, EXPAND_THREADS, e->stream, e->dc, e->t, e->G, src, (const float *)e->d_stats, value_dev, e->Cpuct,
-               (const double *)e->d_logtab);
-    swap_leaf_arrays(e);
-  } else {
-    // a one-leaf selection made before fpc_search_set_leaves switched this search to leaf-parallel: its path holds no
-    // pending visit, so it is expanded by k_expand, and the next step's leaves are selected by k_select_multi
-    FPC_LAUNCH(k_expand, e->G, EXPAND_THREADS, e->stream, e->dc, e->t, e->G, src, (const float *)e->d_stats, value_dev);
-    FPC_LAUNCH(k_select_multi, e->G, 64, e->stream, e->dc, e->t, e->G, e->leaves, e->Cpuct, (const double *)e->d_logtab, leafpar(e));
-  }
+  launch_expand(e, LogitSrc{logits_dev, nullptr, nullptr, 0, 0, 0, 0, 256}, e->d_stats, nullptr, value_dev, e->leaves);
   HIPCHK(e, hipGetLastError());
-  e->rows_k = e->multi ? e->leaves : 1;
-  e->pending_vl = e->multi;
   mark(e, 4);
   e->stats.launches_expand++;
   mark(e, 0);
@@ -601,92 +636,32 @@ int fpc_search_expand_select(fpc_engine *e, const float *logits_dev, const float
 }
 
 int fpc_search_expand(fpc_engine *e, const float *logits_dev, const float *value_dev) {
-  if (!e || !e->searching) return fail(e, FPC_ESTATE, "fpc_search_begin has not been called");
+  int r;
+  if ((r = check_searching(e))) return r;
   USE_DEV(e);
   if (!logits_dev || !value_dev) return fail(e, FPC_EINVAL, "null logits/value");
   mark(e, 3);
   launch_partials(e, logits_dev);
-  const LogitSrc src{logits_dev, nullptr, nullptr, 0, 0, 0, 0, 256};
-  if (e->pending_vl)
-    FPC_LAUNCH(k_expand_multi, e->G, EXPAND_THREADS, e->stream, e->dc, e->t, e->G, e->rows_k, src, (const float *)e->d_stats, value_dev, leafpar(e));
-  else                                       // one leaf per game, or a one-leaf selection made before the switch
-    FPC_LAUNCH(k_expand, e->G, EXPAND_THREADS, e->stream, e->dc, e->t, e->G, src, (const float *)e->d_stats, value_dev);
+  launch_expand(e, LogitSrc{logits_dev, nullptr, nullptr, 0, 0, 0, 0, 256}, e->d_stats, nullptr, value_dev, 0);
   HIPCHK(e, hipGetLastError());
   mark(e, 4);
   e->stats.launches_expand++;
   return 0;
 }
 
-#ifndef FPC_EMUL
-// fpc_search_run of a leaf-parallel search: ceil(sims / K) steps of K leaves per game, the last one of the remainder.
-// Step s: [k_select_multi] -> network over k_s * G rows -> k_expand(_legal)_multi, fused with the next step's selection
-// (k_expand(_legal)_select_multi) for all but the last step.
-static int run_multi(fpc_engine *e, int sims) {
-  const int K = e->leaves, steps = (sims + K - 1) / K, G = e->G;
-  auto leaves_of = [&](int s) { return s + 1 < steps ? K : sims - K * (steps - 1); };
-  const bool legal = e->policy_mode == FPC_POLICY_LEGAL;
-  for (int s = 0; s < steps; ++s) {
-    const int ks = leaves_of(s), rows = ks * G;
-    if (s == 0) {
-      mark(e, 0);
-      FPC_LAUNCH(k_select_multi, G, 64, e->stream, e->dc, e->t, G, ks, e->Cpuct, (const double *)e->d_logtab, leafpar(e));
-    } else {
-      mark(e, 0);
-    }
-    if (e->nn.takes_boards())
-      e->nn.set_board_input((const fpc_board *)e->t.boards, 0, (const int *)e->t.leaf_slot, (const int *)e->t.leaf_turn);
-    else
-      FPC_LAUNCH(k_encode, rows, 64, e->stream, e->dc, (const fpc_board *)e->t.boards, 0, (const int *)e->t.leaf_slot,
-                 (const int *)e->t.leaf_turn, rows, 1, (float *)nullptr, e->nn.input16(), e->nn.one16(), -1);
-    mark(e, 1);
-    e->nn.mark_fn = [](void *ctx, int tag) { mark((fpc_engine *)ctx, tag); };
-    e->nn.mark_ctx = e;
-    int r = legal ? e->nn.forward_legal(rows, e->t, &e->err) : e->nn.forward(rows, false, &e->err);
-    e->nn.mark_fn = nullptr;
-    if (r) return r;
-    mark(e, 3);
-    const bool fuse = s + 1 < steps;
-    const int knext = fuse ? leaves_of(s + 1) : 0;
-    if (legal) {
-      if (fuse)
-        FPC_LAUNCH(k_expand_legal_select_multi, G, 64, e->stream, e->dc, e->t, G, ks, knext, (const float *)e->nn.legal_logits(),
-                   (const float *)e->nn.value(), e->Cpuct, (const double *)e->d_logtab, leafpar(e));
-      else
-        FPC_LAUNCH(k_expand_legal_multi, G, 64, e->stream, e->dc, e->t, G, ks, (const float *)e->nn.legal_logits(), (const float *)e->nn.value(),
-                   leafpar(e));
-    } else {
-      if (fuse)
-        FPC_LAUNCH(k_expand_select_multi, G, EXPAND_THREADS, e->stream, e->dc, e->t, G, ks, knext, e->nn.logit_src(false),
-                   (const float *)e->nn.stats(), (const float *)e->nn.value(), e->Cpuct, (const double *)e->d_logtab, leafpar(e));
-      else
-        FPC_LAUNCH(k_expand_multi, G, EXPAND_THREADS, e->stream, e->dc, e->t, G, ks, e->nn.logit_src(false), (const float *)e->nn.stats(),
-                   (const float *)e->nn.value(), leafpar(e));
-    }
-    if (fuse) swap_leaf_arrays(e);
-    mark(e, 4);
-    e->stats.launches_select++; e->stats.launches_nn++; e->stats.launches_expand++;
-  }
-  e->rows_k = 1;
-  e->pending_vl = false;
-  HIPCHK(e, hipGetLastError());
-  return 0;
-}
-#endif
-
 int fpc_search_set_leaves(fpc_engine *e, int leaves, double virtual_loss) {
   if (!e) return fail(e, FPC_EINVAL, "null engine");
   if (leaves < 1 || leaves > FPC_MAX_LEAVES) return fail(e, FPC_EINVAL, "leaves %d outside 1..%d", leaves, FPC_MAX_LEAVES);
   if (!std::isfinite(virtual_loss) || virtual_loss < 0.0) return fail(e, FPC_EINVAL, "virtual_loss must be finite and >= 0");
-  if (e->stepping && (long)leaves * e->G > e->cfg.max_games)   // a running search; every selection re-checks (check_rows)
-    return fail(e, FPC_EINVAL, "%d leaves x %d games = %ld rows > max_games %d", leaves, e->G, (long)leaves * e->G, e->cfg.max_games);
+  int r;
+  if (e->stepping && (r = check_rows(e, leaves, e->G))) return r;   // a running search; every selection re-checks (admit)
   USE_DEV(e);
   if (leaves > 1 && !e->d_VL) {
-    int r;
     if ((r = dalloc(e, &e->d_VL, (size_t)e->cfg.max_games * e->t.node_cap))) return r;
   }
   if (leaves > 1 && e->searching && !e->multi) {
     // a search that started with one leaf per game: its nodes were created without pending-visit counters (a pending
-    // one-leaf selection holds none either: fpc_search_expand(_select) expands it with k_expand)
+    // one-leaf selection holds none either: launch_expand expands it with the one-leaf kernel)
     HIPCHK(e, hipMemsetAsync(e->d_VL, 0, (size_t)e->cfg.max_games * e->t.node_cap * sizeof(int), e->stream));
     e->multi = true;
   }
@@ -695,53 +670,48 @@ int fpc_search_set_leaves(fpc_engine *e, int leaves, double virtual_loss) {
   return 0;
 }
 
+#ifndef FPC_EMUL
+// the pending leaves as the network's input: the tower megakernels encode them themselves, the other paths take k_encode's
+static void stage_leaves(fpc_engine *e) {
+  const int rows = e->rows_k * e->G;
+  if (e->nn.takes_boards())
+    e->nn.set_board_input((const fpc_board *)e->t.boards, leaf_board_stride(e), (const int *)e->t.leaf_slot, (const int *)e->t.leaf_turn);
+  else
+    FPC_LAUNCH(k_encode, rows, 64, e->stream, e->dc, (const fpc_board *)e->t.boards, leaf_board_stride(e), (const int *)e->t.leaf_slot,
+               (const int *)e->t.leaf_turn, rows, 1, (float *)nullptr, e->nn.input16(), e->nn.one16(), -1);
+}
+#endif
+
 int fpc_search_run(fpc_engine *e, int sims) {
-  if (!e || !e->searching) return fail(e, FPC_ESTATE, "fpc_search_begin has not been called");
+  int r;
+  if ((r = check_searching(e))) return r;
   USE_DEV(e);
   if (sims < 0 || sims > e->cfg.max_sims) return fail(e, FPC_EINVAL, "sims %d > max_sims %d", sims, e->cfg.max_sims);
-  int rc;
-  if ((rc = check_rows(e))) return rc;
-  if (e->sims_issued + sims > e->cfg.max_sims) return fail(e, FPC_ECAPACITY, "more than max_sims = %d simulations since fpc_search_begin", e->cfg.max_sims);
-  e->sims_issued += sims;
+  if ((r = admit(e, sims))) return r;
 #ifdef FPC_EMUL
   return fail(e, FPC_EWEIGHTS, "the internal ResNet exists only in the gfx950 build");
 #else
   if (!e->nn.loaded) return fail(e, FPC_EWEIGHTS, "fpc_load_weights has not been called");
-  if (e->multi) return run_multi(e, sims);
-  // step s: [k_select] -> network -> k_expand; for all but the last step of this call the expansion and the
-  // NEXT step's selection are one launch (k_expand_select), so a step is 4 dependent kernels instead of 5
-  for (int s = 0; s < sims; ++s) {
-    if (s == 0) launch_select(e); else mark(e, 0);
-    if (e->nn.takes_boards())      // the tower megakernel encodes its games' leaves itself
-      e->nn.set_board_input((const fpc_board *)e->t.boards, e->t.board_cap, (const int *)e->t.leaf_slot, (const int *)e->t.leaf_turn);
-    else
-      FPC_LAUNCH(k_encode, e->G, 64, e->stream, e->dc, (const fpc_board *)e->t.boards, e->t.board_cap,
-                 (const int *)e->t.leaf_slot, (const int *)e->t.leaf_turn, e->G, 1, (float *)nullptr, e->nn.input16(),
-                 e->nn.one16(), -1);
+  // ceil(sims / K) steps of K leaves per game, the last one of the remainder (K = 1 in a one-leaf search)
+  const int K = e->leaves, steps = (sims + K - 1) / K;
+  auto leaves_of = [&](int s) { return s + 1 < steps ? K : sims - K * (steps - 1); };
+  const bool legal = e->policy_mode == FPC_POLICY_LEGAL;
+  // developer knob (A/B, with FPC_DEV_KNOBS=1): the dense [rows][A] logits matrix is written as well
+  const bool dense = getenv("FPC_DEV_KNOBS") && atoi(getenv("FPC_DEV_KNOBS")) != 0 && getenv("FPC_DENSE_LOGITS") != nullptr;
+  for (int s = 0; s < steps; ++s) {
+    mark(e, 0);
+    if (s == 0) launch_select(e, leaves_of(0));
+    stage_leaves(e);
     mark(e, 1);
     e->nn.mark_fn = [](void *ctx, int tag) { mark((fpc_engine *)ctx, tag); };
     e->nn.mark_ctx = e;
-    const bool dense = getenv("FPC_DEV_KNOBS") && atoi(getenv("FPC_DEV_KNOBS")) != 0 && getenv("FPC_DENSE_LOGITS") != nullptr;    // developer knob (A/B, with FPC_DEV_KNOBS=1): the dense [G][A] logits matrix is written as well
-    int r = e->policy_mode == FPC_POLICY_LEGAL ? e->nn.forward_legal(e->G, e->t, &e->err) : e->nn.forward(e->G, dense, &e->err);
+    const int rows = e->rows_k * e->G;
+    r = legal ? e->nn.forward_legal(rows, e->t, &e->err) : e->nn.forward(rows, dense, &e->err);
     e->nn.mark_fn = nullptr;
     if (r) return r;
     mark(e, 3);
-    const bool fuse = s + 1 < sims;
-    if (e->policy_mode == FPC_POLICY_LEGAL) {
-      if (fuse)
-        FPC_LAUNCH(k_expand_legal_select, e->G, 64, e->stream, e->dc, e->t, e->G, (const float *)e->nn.legal_logits(), (const float *)e->nn.value(),
-                   e->Cpuct, (const double *)e->d_logtab);
-      else
-        FPC_LAUNCH(k_expand_legal, e->G, 64, e->stream, e->dc, e->t, e->G, (const float *)e->nn.legal_logits(), (const float *)e->nn.value());
-    } else {
-      if (fuse)
-        FPC_LAUNCH(k_expand_select, e->G, EXPAND_THREADS, e->stream, e->dc, e->t, e->G, e->nn.logit_src(dense), (const float *)e->nn.stats(),
-                   (const float *)e->nn.value(), e->Cpuct, (const double *)e->d_logtab);
-      else
-        FPC_LAUNCH(k_expand, e->G, EXPAND_THREADS, e->stream, e->dc, e->t, e->G, e->nn.logit_src(dense), (const float *)e->nn.stats(),
-                   (const float *)e->nn.value());
-    }
-    if (fuse) swap_leaf_arrays(e);
+    launch_expand(e, e->nn.logit_src(dense), (const float *)e->nn.stats(), legal ? (const float *)e->nn.legal_logits() : nullptr,
+                  (const float *)e->nn.value(), s + 1 < steps ? leaves_of(s + 1) : 0);
     mark(e, 4);
     e->stats.launches_select++; e->stats.launches_nn++; e->stats.launches_expand++;
   }

@@ -1329,19 +1329,6 @@ __device__ inline void select_game(WaveLds &s, const DevCfg &c, const Tree &t, i
           Nc += m->cvl;
           Wc = (c.rules & FPC_RULES_PUCT) ? Wc + m->lp.vl * (double)m->cvl : Wc - m->lp.vl * (double)m->cvl;
         }
-#ifdef FPC_TREE_LDS_STAGE
-        // A/B arm only (north_star: "per-game node N/W/P arrays staged in LDS"): the level's children pass through LDS
-        // before the PUCT arithmetic reads them -- one more dependent round trip per level, no reuse to pay for it
-        // (a level is read exactly once per simulation).  Measured in profiles/r05/ab_summary.md; the product keeps them in registers.
-        {
-          int *sN = reinterpret_cast<int *>(&s.scr[0][0][0]);
-          double *sW = reinterpret_cast<double *>(&s.scr[0][0][0]) + 64;
-          float *sP = reinterpret_cast<float *>(&s.scr[0][0][0]) + 64 + 128 + 64;
-          sN[lane] = Nc; sW[lane] = Wc; sP[lane] = (float)Pc;
-          __builtin_amdgcn_s_waitcnt(0xc07f);          // lgkmcnt(0): the stores are in LDS
-          Nc = *const_cast<volatile int *>(&sN[lane]); Wc = *const_cast<volatile double *>(&sW[lane]); Pc = (double)*const_cast<volatile float *>(&sP[lane]);
-        }
-#endif
         cc0 = t.child0[nb + c0 + i];
         cnc = t.nch[nb + c0 + i];
         cslot = t.bslot[nb + c0 + i];
@@ -1710,8 +1697,8 @@ __device__ __forceinline__ float logit_at(const LogitSrc &L, int g, int A, int i
 }
 // G: rows of the step (games when one leaf per game); g the game, row the leaf's row (== g unless MULTI)
 template <bool MULTI>
-__device__ inline bool expand_game_t(WaveLds &s, const DevCfg &c, const Tree &t, int G, int g, int row, const LogitSrc &logits,
-                                     const float *stats, const float *value, int *VL) {
+__device__ inline bool expand_game(WaveLds &s, const DevCfg &c, const Tree &t, int G, int g, int row, const LogitSrc &logits,
+                                   const float *stats, const float *value, int *VL) {
   const int lane = lane_id();
   const size_t nb = (size_t)g * t.node_cap;
   const int nchunks = (c.A / 4 + SM_THREADS - 1) / SM_THREADS;     // A = (8R+8)*R*R is a multiple of 4 for even R
@@ -1757,16 +1744,12 @@ __device__ inline bool expand_game_t(WaveLds &s, const DevCfg &c, const Tree &t,
   FPC_TS(3);
   return expand_finish<MULTI>(s, t, g, row, nb, n, nl, nan, pre, VL);
 }
-__device__ __forceinline__ void expand_game(WaveLds &s, const DevCfg &c, const Tree &t, int G, int g, const LogitSrc &logits, const float *stats,
-                                            const float *value) {
-  (void)expand_game_t<false>(s, c, t, G, g, g, logits, stats, value, nullptr);
-}
 
 __global__ void __launch_bounds__(EXPAND_THREADS) k_expand(DevCfg c, Tree t, int G, LogitSrc logits, const float *stats, const float *value) {
   __shared__ WaveLds s;
   const int g = blockIdx.x;
   if (g >= G) return;
-  expand_game(s, c, t, G, g, logits, stats, value);
+  (void)expand_game<false>(s, c, t, G, g, g, logits, stats, value, nullptr);
 }
 
 // k_expand of simulation step s followed, for the same game, by k_select of step s+1 (one launch and one
@@ -1779,7 +1762,7 @@ __global__ void __launch_bounds__(EXPAND_THREADS) k_expand_select(DevCfg c, Tree
   const int g = blockIdx.x;
   if (g >= G) return;
   FPC_TS(0);
-  expand_game(s, c, t, G, g, logits, stats, value);
+  (void)expand_game<false>(s, c, t, G, g, g, logits, stats, value, nullptr);
   __syncthreads();                           // the new children (global stores of other lanes) are visible to the descent
   FPC_TS(4);
   select_game(s, c, t, g, Cpuct, logtab, true, ONE_LEAF);
@@ -1797,7 +1780,7 @@ __global__ void __launch_bounds__(EXPAND_THREADS) k_expand_select(DevCfg c, Tree
 // cannot see.  One wave per game.
 // ================================================================================================
 template <bool MULTI>
-__device__ inline bool expand_legal_game_t(WaveLds &s, const DevCfg &c, const Tree &t, int g, int row, const float *ll, const float *value, int *VL) {
+__device__ inline bool expand_legal_game(WaveLds &s, const DevCfg &c, const Tree &t, int g, int row, const float *ll, const float *value, int *VL) {
   const int lane = lane_id();
   const int n = t.leaf_node[row];
   const ExpandPre pre = expand_prefetch(t, g, row, value);
@@ -1818,15 +1801,12 @@ __device__ inline bool expand_legal_game_t(WaveLds &s, const DevCfg &c, const Tr
   __syncthreads();
   return expand_finish<MULTI>(s, t, g, row, nb, n, nl, nan, pre, VL);
 }
-__device__ __forceinline__ void expand_legal_game(WaveLds &s, const DevCfg &c, const Tree &t, int g, const float *ll, const float *value) {
-  (void)expand_legal_game_t<false>(s, c, t, g, g, ll, value, nullptr);
-}
 
 __global__ void __launch_bounds__(64) k_expand_legal(DevCfg c, Tree t, int G, const float *ll, const float *value) {
   __shared__ WaveLds s;
   const int g = blockIdx.x;
   if (g >= G) return;
-  expand_legal_game(s, c, t, g, ll, value);
+  (void)expand_legal_game<false>(s, c, t, g, g, ll, value, nullptr);
 }
 
 // the legal-only head's counterpart of k_expand_select
@@ -1835,7 +1815,7 @@ __global__ void __launch_bounds__(64) k_expand_legal_select(DevCfg c, Tree t, in
   __shared__ WaveLds s;
   const int g = blockIdx.x;
   if (g >= G) return;
-  expand_legal_game(s, c, t, g, ll, value);
+  (void)expand_legal_game<false>(s, c, t, g, g, ll, value, nullptr);
   __syncthreads();
   select_game(s, c, t, g, Cpuct, logtab, true, ONE_LEAF);
 }
@@ -1852,8 +1832,8 @@ __device__ inline void expand_game_multi(WaveLds &s, const DevCfg &c, const Tree
   for (int k = 0; k < kexp; ++k) {
     const int row = k * G + g;
     bool ok;
-    if constexpr (LEGAL) ok = expand_legal_game_t<true>(s, c, t, g, row, ll, value, VL);
-    else ok = expand_game_t<true>(s, c, t, kexp * G, g, row, logits, stats, value, VL);
+    if constexpr (LEGAL) ok = expand_legal_game<true>(s, c, t, g, row, ll, value, VL);
+    else ok = expand_game<true>(s, c, t, kexp * G, g, row, logits, stats, value, VL);
     __syncthreads();                         // this row's tree stores (N, W, VL, children, nnodes) precede the next row
     if (!ok) break;                          // policy error: the game has left the search
   }
