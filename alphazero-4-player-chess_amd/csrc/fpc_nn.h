@@ -439,6 +439,7 @@ struct NN {
   bool use_tower = false;            // hidden == 128: k_tower
   int tower_waves = 8;               // developer knob FPC_TOWER_WAVES (A/B): 4 = one wave per SIMD
   bool tower_compact = true;         // 14x14: k_towerc (k_tower's skeleton on the compact image, 13 row tiles); developer knob FPC_TOWER_COMPACT=0: k_tower
+  bool tower_taploop = true;         // k_towerc with the tap-specialised loop; developer knob FPC_TOWER_TAPLOOP=0: the rolled loop (A/B)
   int towerw_rows = 1;               // developer knob FPC_TOWERW_ROWS=2: hidden 256 on two wave rows x four (A/B)
   bool use_towerw = false;           // k_towerw runs the tower (hidden 256; hidden 128 on every board but 14x14)
   void (*mark_fn)(void *, int) = nullptr;   // stage-timing hook of the engine (tag 2 = policy Linear starts)
@@ -597,6 +598,7 @@ struct NN {
     const bool no_tower = knob("FPC_NO_TOWER", 0) != 0;
     tower_waves = knob("FPC_TOWER_WAVES", 8);
     tower_compact = knob("FPC_TOWER_COMPACT", 1) != 0;
+    tower_taploop = knob("FPC_TOWER_TAPLOOP", 1) != 0;
     // Which megakernel runs the tower (one launch, activations LDS-resident; everything else: k_conv3x3 per layer):
     //   hidden 256: k_towerw (two waves per SIMD, weights L2 -> registers; any board size).
     //   hidden 128: 14x14: k_tower (LDS-DMA weight ring, loader / staggered wave roles; its grid rows ARE the 16-position row
@@ -715,7 +717,8 @@ struct NN {
         (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_tower<DT, 3, false, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, TW_LDS);
         (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_tower<DT, 5, false, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, TW_LDS);
         (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_tower<DT, 7, false, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, TW_LDS);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_towerc<DT>), hipFuncAttributeMaxDynamicSharedMemorySize, TW_LDS);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_towerc<DT, false>), hipFuncAttributeMaxDynamicSharedMemorySize, TW_LDS);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_towerc<DT, true>), hipFuncAttributeMaxDynamicSharedMemorySize, TW_LDS);
         attr = true;
       }
       if (use_towerw) {
@@ -759,7 +762,8 @@ struct NN {
       else if (P != 16 && tower_waves == 8) hipLaunchKernelGGL((k_tower<DT, 7, false, 8>), dim3(n), dim3(512), TW_LDS, stream, t);
       else if (P != 16) hipLaunchKernelGGL((k_tower<DT, 7, false, 4>), dim3(n), dim3(256), TW_LDS, stream, t);
       // 14x14: the compact image (13 row tiles: loaders 6, staggered half 7) ...
-      else if (tower_waves == 8 && tower_compact && dc.R == 14) hipLaunchKernelGGL((k_towerc<DT>), dim3(n), dim3(512), TW_LDS, stream, t);
+      else if (tower_waves == 8 && tower_compact && dc.R == 14 && tower_taploop) hipLaunchKernelGGL((k_towerc<DT, true>), dim3(n), dim3(512), TW_LDS, stream, t);
+      else if (tower_waves == 8 && tower_compact && dc.R == 14) hipLaunchKernelGGL((k_towerc<DT, false>), dim3(n), dim3(512), TW_LDS, stream, t);
       // ... or the bordered grid (grid pitch == tile height): two waves per SIMD, 7 x 2 tiles each
       else if (tower_waves == 8) hipLaunchKernelGGL((k_tower<DT, 7, true, 8>), dim3(n), dim3(512), TW_LDS, stream, t);
       else hipLaunchKernelGGL((k_tower<DT, 7, true, 4>), dim3(n), dim3(256), TW_LDS, stream, t);

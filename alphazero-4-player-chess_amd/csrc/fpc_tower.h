@@ -226,6 +226,12 @@ __device__ __forceinline__ void tw_dma_256(const unsigned char *gsrc_uniform, ui
 #define TWC_LOADER_TILES 6
 #endif
 
+// k_towerc's tap-specialised loop: its own stagger (1..3, placed as TW_STAGGER places it).  With the loader's per-tap scalar
+// arithmetic gone, 2 measured 0.7 % faster than 3 at 6 / 7 tiles (same-box A/B, every run); 5 / 8 and 7 / 6 tiles spill.
+#ifndef TWC_STAGGER
+#define TWC_STAGGER 2
+#endif
+
 // NW: waves per workgroup.  4 = one wave per SIMD, wave (wm, wn) owns MT row tiles x 4 column tiles (64 output
 // channels).  8 = two waves per SIMD, each with half the register file: wave (wm, wn) owns MT row tiles x 2 column
 // tiles (32 channels).  The 8-wave form pays 18 instead of 11 fragment reads per SIMD and k-step, but what one
@@ -241,9 +247,16 @@ __device__ __forceinline__ void tw_dma_256(const unsigned char *gsrc_uniform, ui
 // of 16 squares instead of 14 grid rows: the loader half (waves 0-3, which also carries the weight DMA) owns tiles 0..5,
 // the staggered half tiles 6..12 -- 7 % fewer MFMAs and fragment reads per layer, same MFMAs per output element in the
 // same order (bit-identical logits; the value head sums the same terms in another order).
-template <int DT, int MT, bool FAST, int NW, int LOAD, bool CMP = false>
+// TU (CMP only): the tap-specialised loop.  A layer's nine taps run as three dy iterations of an unrolled dx triple, and
+// because a layer has 9 taps and the ring 3 slots, the ring slot of a tap is dx + 1 in every layer: the slot of the weight
+// fragments, the LDS destination of the DMA burst, the column masks and whether a tap needs selects at all (dx = 0: none)
+// are constants of the instruction stream.  What is left per tap at run time: five VALU operations for the shifted row's
+// offset, one select per row tile for dx = +-1, one 64-bit scalar add for the DMA source.  Same barriers, same MFMAs on
+// the same operands in the same order as the rolled loop (bit-identical logits AND values).
+template <int DT, int MT, bool FAST, int NW, int LOAD, bool CMP = false, bool TU = false>
 __device__ __forceinline__ void tw_body(const TowerArgs &g) {
   static_assert(!CMP || (!FAST && NW == 8 && TW_LOADERS == 1 && MT == (LOAD == 2 ? TWC_LOADER_TILES : 13 - TWC_LOADER_TILES)), "compact form: 8 waves, 13 row tiles");
+  static_assert(!TU || (CMP && TW_STAGGER != 0 && TWC_STAGGER >= 1 && TWC_STAGGER <= 3), "tap-specialised loop: compact form with the burst stream");
   constexpr int CR = 14, CZ = 16;                   // CMP: board side, zero rows in front of square 0
   constexpr int TB0 = LOAD == 2 ? 0 : TWC_LOADER_TILES;   // CMP: first row tile of this wave half
   constexpr int NT = NW * 64;                      // threads
@@ -253,7 +266,7 @@ __device__ __forceinline__ void tw_body(const TowerArgs &g) {
   constexpr int DMA_PER_WAVE = PIECES * 1024;
   constexpr int MID = PIECES == 8 ? 4096 : 0;      // the stream base sits in the middle of an 8-KiB share (immediates reach -4096 .. 4095)
   constexpr bool STREAM = TW_AHEAD == 2 && !(TW_STAGGER != 0 && NW == 8 && TW_LOADERS == 1);   // pieces between the MFMAs, two taps ahead
-  constexpr int STAG = (NW == 8 && TW_LOADERS == 1 && LOAD == 0) ? TW_STAGGER : 0;        // k-steps this wave passes the tap barrier early (0..3)
+  constexpr int STAG = (NW == 8 && TW_LOADERS == 1 && LOAD == 0) ? (TU ? TWC_STAGGER : TW_STAGGER) : 0;        // k-steps this wave passes the tap barrier early (0..3)
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   unsigned char *const img = smem + TW_IMG0;
   unsigned char *const ring = smem + TW_RING;
@@ -500,6 +513,27 @@ __device__ __forceinline__ void tw_body(const TowerArgs &g) {
       }
     }
   };
+  // TU: the same for the tap with compile-time dx = XN - 1 (XN = its ring slot) in board row shift dy, rrow = rbase + CR * dy
+  // (slot 2 lies past the 64 KiB that a ds_read immediate reaches from slot 0: a base of its own, kept opaque, or
+  // hipcc holds one address register per fragment)
+  const unsigned char *wrow = nullptr, *wrow2 = nullptr;   // TU: this wave's weight rows of the current layer in ring slots 0 and 2
+  auto set_wrow = [&](int cb) {
+    int o = cb * 256 + apart, o2 = o + 2 * TW_TAP;
+    asm volatile("" : "+v"(o2));
+    wrow = ring + o;
+    wrow2 = ring + o2;
+  };
+  int rrow = rbase - CR;
+  auto set_tap_u = [&](auto xn_c) {
+    constexpr int XN = decltype(xn_c)::value;
+    wslot = XN == 2 ? wrow2 : wrow + XN * TW_TAP;
+    const int r = rrow + (XN - 1);
+    const uint32_t zoff = (r & 7) * 16 + bq;
+    const uint32_t b0 = (r >> 3) * 2048 + zoff;
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt)
+      boff[mt] = XN == 1 ? (int)(b0 + mt * 4096) : (int)lane_select(b0 + mt * 4096, zoff, colmask(mt, XN - 1));
+  };
   auto bptr = [&](int mt) -> const unsigned char * {
     if (FAST) return mt == MT - 1 ? blast : bbase + mt * 4096;
     return img + boff[mt];
@@ -555,8 +589,48 @@ __device__ __forceinline__ void tw_body(const TowerArgs &g) {
   // addresses are set for tap 0; on exit the same holds for the NEXT layer (whose first weight row of
   // this wave is cb_next), except that fb[0] was read from the image the epilogue is about to rewrite
   // (load_b0 after it).
+  // TU: one tap with ring slot X = dx + 1 up to its k-step 3 (which reads k-step 0 of the tap in slot (X + 1) % 3)
+  const unsigned char *usrc = g.Wt + (size_t)TW_TAP + lw * DMA_PER_WAVE;                          // loader: its share of the youngest tap in flight
+  const uint32_t udst = (uint32_t)__builtin_amdgcn_readfirstlane(TW_RING + lw * DMA_PER_WAVE);    // ... and of ring slot 0
+  auto tap_u = [&](auto mode_c, auto x_c, const t_f32x4 *b4, const int dy, const int cb_next) {
+    constexpr int X = decltype(x_c)::value;
+    if (STAG == 2) {
+      TW_STAMP(gt, 3);
+      __syncthreads();
+      TW_STAMP(gt, 4);
+    }
+    TW_STAMP(gt, 0);
+    kstep(mode_c, c1, c2, c0, b4, c2);             // k-step 1
+    TW_STAMP(gt, 1);
+    if (STAG == 1) __syncthreads();
+    kstep(mode_c, c0, c3, c0, b4, c3);             // k-step 2
+    TW_STAMP(gt, 2);
+    if (!STAG) {                                   // as in the rolled loop: the next tap has landed, this tap's slot is free in two taps' time
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      TW_STAMP(gt, 3);
+      if (!(TW_STRIP & 8)) __syncthreads();
+      TW_STAMP(gt, 4);
+      if (LOAD != 0 && !(TW_STRIP & 4)) {          // the tap two ahead -> slot (X + 2) % 3; the last layer's run into the host's padding
+        usrc += TW_TAP;
+        tw_dma_8k(usrc, dma_lane, udst + ((X + 2) % 3) * TW_TAP);
+      }
+      TW_STAMP(gt, 5);
+    }
+    ++gt;
+    if (X == 2) {                                  // the next tap opens a board row -- or the next layer
+      rrow = dy == 1 ? rbase - CR : rrow + CR;
+      if (dy == 1) set_wrow(cb_next);              // (wave-uniform)
+    }
+    set_tap_u(std::integral_constant<int, (X + 1) % 3>{});
+    TW_STAMP(gt - 1, 6);
+    kstep(mode_c, c1, c0, c0, b4, c0);             // k-step 3, reading (next tap, k-step 0)
+    TW_STAMP(gt - 1, 7);
+  };
   auto run_layer = [&](auto mode_c, const int layer, const int cb, const int cb_next) {
     constexpr int MODE = decltype(mode_c)::value;
+    if (TU && wave < 4 && layer + 1 < g.L + 2)     // the next layer's biases go into the half of the buffer that layer - 1 used
+      tw_dma_256(reinterpret_cast<const unsigned char *>(g.bt + (size_t)(layer + 1) * 256 + wave * 64), (uint32_t)lane * 4u,
+                 (uint32_t)__builtin_amdgcn_readfirstlane(TW_BIAS + (((layer + 1) & 1) * 256 + wave * 64) * 4));
     t_f32x4 b4[CT];
     {
       const float *bl = biasbuf + (layer & 1) * 256 + cb + 4 * lq;
@@ -565,6 +639,26 @@ __device__ __forceinline__ void tw_body(const TowerArgs &g) {
     }
     if (STAG == 3 && !(TW_STRIP & 8)) __syncthreads();                // (a staggered wave issued no DMA: nothing to wait for)
     kstep(mode_c, c0, c1, c1, b4, c1);             // (tap 0, k-step 0), C = bias
+    if (TU) {
+#pragma unroll 1
+      for (int dy = -1;; ++dy) {
+        tap_u(mode_c, c0, b4, dy, cb_next);
+        if (STAG == 3 && !(TW_STRIP & 8)) __syncthreads();
+        kstep(mode_c, c0, c1, c0, b4, c1);         // (next tap, k-step 0)
+        TW_STAMP(gt - 1, 8);
+        tap_u(mode_c, c1, b4, dy, cb_next);
+        if (STAG == 3 && !(TW_STRIP & 8)) __syncthreads();
+        kstep(mode_c, c0, c1, c0, b4, c1);
+        TW_STAMP(gt - 1, 8);
+        tap_u(mode_c, c2, b4, dy, cb_next);
+        if (dy == 1) break;
+        if (STAG == 3 && !(TW_STRIP & 8)) __syncthreads();
+        kstep(mode_c, c0, c1, c0, b4, c1);
+        TW_STAMP(gt - 1, 8);
+      }
+      TW_STAMP(gt - 1, 8);
+      return;
+    }
 #pragma unroll 1
     for (int tap = 0; tap < 9; ++tap) {
       if (STAG == 2) {
@@ -604,7 +698,12 @@ __device__ __forceinline__ void tw_body(const TowerArgs &g) {
     }
   };
 
-  set_tap(0, cb64);
+  if (TU) {
+    set_wrow(cb64);
+    set_tap_u(c0);
+  } else {
+    set_tap(0, cb64);
+  }
 #pragma unroll
   for (int ct = 0; ct < CT; ++ct) fa[0][ct] = *reinterpret_cast<const t_u32x4 *>(wslot + ct * 4096);
   load_b0();
@@ -681,11 +780,12 @@ __global__ void __launch_bounds__(NW * 64, NW / 4) k_tower(TowerArgs g) {
   }
 }
 
-// the compact form at 14x14 (CMP): loaders = row tiles 0 .. TWC_LOADER_TILES - 1, staggered half = the rest of the 13
-template <int DT>
+// the compact form at 14x14 (CMP): loaders = row tiles 0 .. TWC_LOADER_TILES - 1, staggered half = the rest of the 13;
+// TU: the tap-specialised loop (the product), false: the rolled loop (same-box A/Bs, bit-identity tests)
+template <int DT, bool TU>
 __global__ void __launch_bounds__(512, 2) k_towerc(TowerArgs g) {
-  if (__builtin_amdgcn_readfirstlane(threadIdx.x >> 6) < 4) tw_body<DT, TWC_LOADER_TILES, false, 8, 2, true>(g);
-  else tw_body<DT, 13 - TWC_LOADER_TILES, false, 8, 0, true>(g);
+  if (__builtin_amdgcn_readfirstlane(threadIdx.x >> 6) < 4) tw_body<DT, TWC_LOADER_TILES, false, 8, 2, true, TU>(g);
+  else tw_body<DT, 13 - TWC_LOADER_TILES, false, 8, 0, true, TU>(g);
 }
 
 // weights [taps][128 rows][cin] 16-bit row-major -> per tap the LDS image (tw_lay with cin/8 chunks per row)
