@@ -1,0 +1,586 @@
+"""Probe heads: networks whose policy head turns the dense logits fpc_nn_forward returns into a window on the
+residual tower, and the float64 reference those logits are held against.
+
+* tower probe: the policy conv copies `width` tower channels from offset c0 (centre tap 1, everything else 0, BN an exact
+  identity) and the policy Linear is the identity, so logits[n, ch*R*R + pos] IS the 16-bit tower activation
+  [n, c0+ch, pos]: every other product of the Linear is an exact zero and no summation order can matter.
+* permutation Linear: the identity replaced by a permutation matrix with entries +-2^k, still exact.
+* policy-conv probe: identity Linear behind a policy conv that carries real weights (family A or B).
+* family A (integer_net): 0/1 inputs, sparse conv weights in {-1, 0, +1}, integer biases, identity BNs -- every
+  activation an integer below 2^11 (fp16) / 2^8 (bf16): f32 accumulation is exact in any order, the kernel must equal
+  the reference BIT FOR BIT.
+* family B (dense_net): Kaiming weights and randomised BN statistics; the bound is measured per case from the noise one
+  more f32 summation order makes on the CPU (noise_figures / check_bounded).
+
+A ResNet at 14x14 owns a 23 520 x 23 520 Linear (2.2 GB in fp32).  The networks here are therefore built on a stub
+geometry (convolutions of the real shape, Linears of a 1 x 1 board), exported with weights.export_weights, and their
+conv sections spliced in front of the Linear sections of ONE exported identity / permutation Linear per (board, operand
+type, layout): splice() -- held bit for bit against a plain export_weights of the whole network by the CPU self-test."""
+import struct
+
+import numpy as np
+import torch
+import torch.nn.functional as TF
+
+import net
+import weights
+
+# operand types by the engine's nn_dtype: significand bits (implicit one included) and the exponent of the smallest quantum
+FMT = {1: {"name": "fp16", "p": 11, "qmin": -24, "torch": torch.float16, "int_max": 2047},
+       0: {"name": "bf16", "p": 8, "qmin": -133, "torch": torch.bfloat16, "int_max": 255}}
+
+
+class Spec:
+    """the gameType attributes net.ResNet reads"""
+    def __init__(self, R, linear_side=None):
+        s = R if linear_side is None else linear_side
+        self.R, self._s = R, s
+        self.num_state_channels = 24
+        self.num_action_channels = 8 * R + 8
+        self.action_space_size = self.num_action_channels * s * s
+        self.state_space_size = 24 * s * s
+
+    def nRows(self):
+        return self._s
+
+    def nCols(self):
+        return self._s
+
+
+def stub_spec(R):
+    """convolutions of an R x R board's network, Linears of a 1 x 1 board"""
+    return Spec(R, 1)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the number formats
+# ---------------------------------------------------------------------------------------------------------------------
+def quantum(x, dtype):
+    """spacing of the operand type's values at |x| (float64 in, float64 out): one rounding of the type at that magnitude"""
+    f = FMT[dtype]
+    x = np.abs(np.asarray(x, np.float64))
+    _, e = np.frexp(x)
+    e = np.where(x == 0, -100000, e)              # frexp(0) has exponent 0: zero sits on the finest grid
+    return np.ldexp(1.0, np.maximum(e - f["p"], f["qmin"]))
+
+
+def round16(x, dtype):
+    """float64 -> the nearest value of the operand type (ties to even), ONE rounding; returned as float64"""
+    x = np.asarray(x, np.float64)
+    q = quantum(x, dtype)
+    return np.rint(x / q) * q
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# networks
+# ---------------------------------------------------------------------------------------------------------------------
+def _convs(m):
+    """(conv, bn) in the blob's order: stem, c1/c2 per block, policy conv, value conv"""
+    out = [(m.startBlock[0], m.startBlock[1])]
+    for b in m.backBone:
+        out += [(b.conv1, b.bn1), (b.conv2, b.bn2)]
+    return out + [(m.policyHead[0], m.policyHead[1]), (m.valueHead[0], m.valueHead[1])]
+
+
+def identity_bn(bn):
+    """an EXACT identity: eps = 0, unit variance, zero mean, weight 1, bias 0 (the fold multiplies by 1/sqrt(1) = 1)"""
+    bn.eps = 0.0
+    with torch.no_grad():
+        bn.running_var.fill_(1.0)
+        bn.running_mean.zero_()
+        bn.weight.fill_(1.0)
+        bn.bias.zero_()
+
+
+def assert_fold_is_identity(conv, bn):
+    w, b = weights._fold(conv, bn)
+    assert torch.equal(w.view(torch.int32), conv.weight.detach().view(torch.int32))
+    assert torch.equal(b.view(torch.int32), conv.bias.detach().view(torch.int32))
+
+
+def dense_net(R, blocks, hidden, seed=0):
+    """family B: Kaiming conv init and randomised BN statistics, like _model() of test_nn_gpu.py"""
+    torch.manual_seed(seed)
+    m = net.ResNet(stub_spec(R), blocks, hidden, "cpu")
+    g = torch.Generator().manual_seed(seed + 1)
+    with torch.no_grad():
+        for mod in m.modules():
+            if isinstance(mod, torch.nn.BatchNorm2d):
+                mod.running_mean.copy_(torch.randn(mod.num_features, generator=g) * 0.1)
+                mod.running_var.copy_(torch.rand(mod.num_features, generator=g) * 0.5 + 0.75)
+                mod.weight.copy_(torch.rand(mod.num_features, generator=g) * 0.5 + 0.75)
+                mod.bias.copy_(torch.randn(mod.num_features, generator=g) * 0.1)
+    return m.eval()
+
+
+def _sparse_int_conv(conv, bn, pos, neg, cin_live, bias_lo, bias_hi, rng):
+    cout, cin = conv.weight.shape[:2]
+    w = np.zeros((cout, cin * 9), np.float32)
+    for co in range(cout):
+        idx = rng.choice(cin_live * 9, size=pos + neg, replace=False)
+        w[co, idx[:pos]] = 1.0
+        w[co, idx[pos:]] = -1.0
+    with torch.no_grad():
+        # (cin, tap) drawn jointly: index = ci * 9 + tap
+        conv.weight.copy_(torch.from_numpy(w).view(cout, cin, 3, 3))
+        conv.bias.copy_(torch.from_numpy(rng.integers(bias_lo, bias_hi + 1, size=cout).astype(np.float32)))
+    identity_bn(bn)
+    assert_fold_is_identity(conv, bn)
+
+
+def integer_net(R, blocks, hidden, seed=0, stem=(6, 2), res=(3, 4), head=(3, 4), bias=(-1, 1)):
+    """family A: every conv weight in {-1, 0, +1} with (positive, negative) nonzeros per output channel at random
+    (tap, cin), integer biases in [bias[0], bias[1]], every BN an exact identity"""
+    torch.manual_seed(seed)
+    m = net.ResNet(stub_spec(R), blocks, hidden, "cpu")
+    rng = np.random.default_rng(seed + 1000)
+    cb = _convs(m)
+    _sparse_int_conv(cb[0][0], cb[0][1], stem[0], stem[1], 24, bias[0], bias[1], rng)
+    for conv, bn in cb[1:-2]:
+        _sparse_int_conv(conv, bn, res[0], res[1], hidden, bias[0], bias[1], rng)
+    for conv, bn in cb[-2:]:
+        _sparse_int_conv(conv, bn, head[0], head[1], hidden, bias[0], bias[1], rng)
+    return m.eval()
+
+
+def probe_offsets(R, hidden):
+    """channel offsets c0 of the tower probes that together see every tower channel: 0, hidden - width, and the middle
+    ones a tower wider than two windows needs"""
+    width = min(8 * R + 8, hidden)
+    offs = list(range(0, hidden - width, width)) + [hidden - width]
+    return offs, width
+
+
+def set_tower_probe(m, c0):
+    """overwrite the policy conv + BN of m: output channel j copies tower channel c0 + j (centre tap); returns the width"""
+    conv, bn = m.policyHead[0], m.policyHead[1]
+    a_ch, hidden = conv.weight.shape[:2]
+    width = min(a_ch, hidden - c0)
+    with torch.no_grad():
+        conv.weight.zero_()
+        conv.bias.zero_()
+        for j in range(width):
+            conv.weight[j, c0 + j, 1, 1] = 1.0
+    identity_bn(bn)
+    assert_fold_is_identity(conv, bn)
+    return width
+
+
+def probe_inputs(R, n, seed=0, density=0.25):
+    """0/1 planes [n, 24, R, R]: row 0 all ones (every border tap live at once), rows 1..8 single-square impulses in the
+    four corners and on the four edges, the rest random with the given density"""
+    rng = np.random.default_rng(seed)
+    x = (rng.random((n, 24, R, R)) < density).astype(np.float32)
+    h = R // 2
+    squares = [(0, 0), (0, R - 1), (R - 1, 0), (R - 1, R - 1), (0, h), (R - 1, h), (h, 0), (h, R - 1)]
+    k = min(n, 1 + len(squares))
+    x[:k] = 0.0
+    x[0] = 1.0
+    for i, (r, c) in enumerate(squares[: k - 1]):
+        x[1 + i, :, r, c] = 1.0
+    return x
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the reference: DESIGN.md 5.2 -- 16-bit operands, bias + sum (+ residual), ReLU, ONE rounding to 16 bits per layer
+# ---------------------------------------------------------------------------------------------------------------------
+def conv_layers(m, dtype):
+    """[(w, b)] in blob order: w = the folded weights rounded to the operand type as weights.export_weights rounds them
+    (float64 tensors holding 16-bit values), b = the folded f32 bias as float64.  The fold itself is weights._fold, the
+    export's own: that it equals the torch model's conv + BN is held by the tests against the torch model
+    (test_nn_gpu.py, test_net_gpu.py), not here -- these tests hold what the kernels do with the exported operands."""
+    out = []
+    for conv, bn in _convs(m):
+        w, b = weights._fold(conv, bn)
+        w = w if dtype is None else w.to(FMT[dtype]["torch"])     # None: unrounded (the fp32 network's stand-in)
+        out.append((w.to(torch.float64), b.to(torch.float32).to(torch.float64)))
+    return out
+
+
+MUTATIONS = ("zero_element", "wrap_row", "swap_slices", "drop_bias16", "no_residual_tail")
+
+# The fp32 summation orders of the CPU figure besides torch's fused conv ("f32"): (tap order, input channels per addition,
+# accumulator pre-loaded with bias + residual | both added in the epilogue).  "f32seq" is the tower kernels' order (one
+# MFMA k-step of 16 channels per addition), "f32seq4" k_conv3x3's with 4 channels per addition (how an MFMA adds the 16
+# products of a k-step to the accumulator is not specified; 4 values are the smallest per-lane operand of its 16-bit
+# forms).  "f32p0".."f32p4" permute the taps (numpy default_rng(i)) and use 8 / 1 / 2 / 4 / 8 channels per addition.
+ORDERS = {"f32seq": (tuple(range(9)), 16, True), "f32seq4": (tuple(range(9)), 4, False)}
+for _i, (_step, _bf) in enumerate(((8, True), (1, False), (2, True), (4, True), (8, False))):
+    ORDERS["f32p%d" % _i] = (tuple(int(t) for t in np.random.default_rng(_i).permutation(9)), _step, _bf)
+BASE_ORDERS = ("f32", "f32seq", "f32seq4")
+SHALLOW_ORDERS = BASE_ORDERS + tuple("f32p%d" % i for i in range(5))     # networks of at most 3 blocks
+
+
+def _layer(x, w, b, res, dtype, acc, mut):
+    """one conv layer on float64 tensors holding 16-bit values; acc: "f64" | "f32" (torch's fused fp32 conv) | a key of
+    ORDERS | "f32taps" (fp32, nine fused 1x1 convs added tap after tap; carries the mutations in fp32).
+    mut: None or a mutation name, applied to this layer."""
+    R = x.shape[-1]
+    if mut == "swap_slices":                      # two 8-channel input slices of one tap swapped
+        w = w.clone()
+        w[:, 0:8, 1, 2], w[:, 8:16, 1, 2] = w[:, 8:16, 1, 2].clone(), w[:, 0:8, 1, 2].clone()
+    if mut == "drop_bias16":                      # the bias of 16 output channels dropped
+        b = b.clone()
+        b[16:32] = 0.0
+    if acc == "f64":
+        y = TF.conv2d(x, w, padding=1)
+    elif acc == "f32":
+        y = TF.conv2d(x.float(), w.float(), padding=1)
+    elif acc in ORDERS:
+        # ONE fp32 accumulator per output, fed tap after tap and group of input channels after group in sequence
+        taps, step, bias_first = ORDERS[acc]
+        n, cin = x.shape[:2]
+        xp = TF.pad(x.float(), (1, 1, 1, 1))
+        if bias_first:
+            y = b.float().view(1, 1, 1, -1).expand(n, R, R, -1).reshape(n * R * R, -1).clone()
+            if res is not None:
+                y = y + res.float().permute(0, 2, 3, 1).reshape(n * R * R, -1)
+        else:
+            y = torch.zeros(n * R * R, w.shape[0])
+        for t in taps:
+            ky, kx = divmod(t, 3)
+            if step == 16:                        # does not divide the stem's 24 planes: 16, then 8
+                groups = [(c, min(c + 16, cin)) for c in range(0, cin, 16)]
+                xs = xp[:, :, ky:ky + R, kx:kx + R].permute(0, 2, 3, 1).reshape(n * R * R, cin)
+                for c0, c1 in groups:
+                    y = y + xs[:, c0:c1] @ w[:, c0:c1, ky, kx].float().t()
+            else:                                 # the partial sums of all groups of one tap in one bmm, added one by one
+                xg = xp[:, :, ky:ky + R, kx:kx + R].reshape(n, cin // step, step, R * R).permute(1, 0, 3, 2).reshape(cin // step, n * R * R, step)
+                part = torch.bmm(xg, w[:, :, ky, kx].float().view(-1, cin // step, step).permute(1, 2, 0).contiguous())
+                for g in range(cin // step):
+                    y += part[g]
+        y = y.view(n, R, R, -1).permute(0, 3, 1, 2)
+        if not bias_first:
+            y = y + b.float().view(1, -1, 1, 1)
+            if res is not None:
+                y = y + res.float()
+        assert mut is None
+        y = torch.relu(y).double()
+        return y if dtype is None else torch.from_numpy(round16(y.numpy(), dtype))
+    else:
+        xp = TF.pad(x.float(), (1, 1, 1, 1))
+        y = None
+        for ky in range(3):
+            for kx in range(3):
+                t = TF.conv2d(xp[:, :, ky:ky + R, kx:kx + R], w[:, :, ky:ky + 1, kx:kx + 1].float())
+                y = t if y is None else y + t
+    if mut == "wrap_row":                         # row R // 2: the right-edge tap reads the next row's first column
+        r = R // 2
+        for ky in range(3):
+            if 0 <= r + ky < R:
+                y[:, :, r, R - 1] += (x[:, :, r + ky, 0].to(y.dtype) @ w[:, :, ky, 2].to(y.dtype).t())
+    y = y + b.to(y.dtype).view(1, -1, 1, 1)
+    if res is not None:
+        rr = res.to(y.dtype)
+        if mut == "no_residual_tail":             # the residual omitted on the last 4 squares
+            rr = rr.clone().flatten(2)
+            rr[:, :, -4:] = 0.0
+            rr = rr.view(res.shape)
+        y = y + rr
+    y = torch.relu(y).double()
+    if dtype is not None:                         # None: no rounding at all (the fp32 network's stand-in)
+        y = torch.from_numpy(round16(y.numpy(), dtype))
+    if isinstance(mut, tuple):                    # ("zero_small", t): the smallest activation >= t forced to 0
+        flat = y.flatten()
+        flat[int(torch.argmin(torch.where(flat >= mut[1], flat, torch.full_like(flat, float("inf")))))] = 0.0
+        y = flat.view(y.shape)
+    if mut == "zero_element":                     # one live activation forced to 0
+        c = 77 % y.shape[1]                       # channel 77, at the input and square where it is largest
+        n, r, col = np.unravel_index(int(torch.argmax(y[:, c])), (y.shape[0], R, R))
+        assert y[n, c, r, col] > 0
+        y[n, c, r, col] = 0.0
+    return y
+
+
+def forward(layers, x, dtype, acc="f64", mutation=None):
+    """layers: conv_layers(m, dtype); x: 0/1 planes [n, 24, R, R].  mutation: (name, layer index into layers), or
+    ("zero_small", layer index, threshold), or None.
+    Returns {"acts": every tower layer's output, "tower", "policy", "vconv"} as float64 numpy arrays of 16-bit values,
+    and "vconv_unrounded": the value conv's output before its rounding."""
+    x = torch.from_numpy(np.asarray(x, np.float64))
+    nb = (len(layers) - 3) // 2
+
+    def mut(i):
+        if mutation is None or mutation[1] != i:
+            return None
+        return mutation[0] if len(mutation) == 2 else (mutation[0], mutation[2])
+
+    with torch.no_grad():
+        acts = [_layer(x, layers[0][0], layers[0][1], None, dtype, acc, mut(0))]
+        for i in range(nb):
+            t = _layer(acts[-1], layers[1 + 2 * i][0], layers[1 + 2 * i][1], None, dtype, acc, mut(1 + 2 * i))
+            acts.append(t)
+            acts.append(_layer(t, layers[2 + 2 * i][0], layers[2 + 2 * i][1], acts[-2], dtype, acc, mut(2 + 2 * i)))
+        tower = acts[-1]
+        policy = _layer(tower, layers[-2][0], layers[-2][1], None, dtype, acc, mut(len(layers) - 2))
+        vconv = _layer(tower, layers[-1][0], layers[-1][1], None, dtype, acc, mut(len(layers) - 1))
+        # the switch of DESIGN.md 5.2: the tower kernels feed the value Linear from the fp32 accumulators, the value
+        # conv's output is never rounded to 16 bits there; the per-layer path (k_conv3x3 -> k_value_tail) rounds it
+        vraw = _layer(tower, layers[-1][0], layers[-1][1], None, None, acc, mut(len(layers) - 1))
+    return {"acts": [a.numpy() for a in acts], "tower": tower.numpy(), "policy": policy.numpy(), "vconv": vconv.numpy(),
+            "vconv_unrounded": vraw.numpy()}
+
+
+def value_of(vconv, vw, vb, acc="f64"):
+    """tanh(Linear(Flatten(vconv))): vconv [n, 24, R, R] float64, vw the value Linear's f32 weights [24 * R * R]"""
+    flat = vconv.reshape(vconv.shape[0], -1)
+    if acc == "f64":
+        return np.tanh(flat @ vw.astype(np.float64) + float(vb))
+    return np.tanh((flat.astype(np.float32) @ vw.astype(np.float32) + np.float32(vb)).astype(np.float32)).astype(np.float64)
+
+
+def integer_conditions(ref, dtype):
+    """family A's input conditions, from the reference alone: every layer's largest activation (the head convs included)
+    within the operand type's exact integers, >= 40 % of the final tower activations nonzero, >= 32 distinct values"""
+    lim = FMT[dtype]["int_max"]
+    maxima = [float(a.max()) for a in ref["acts"]] + [float(ref["policy"].max()), float(ref["vconv"].max())]
+    for a in ref["acts"] + [ref["policy"], ref["vconv"]]:
+        assert np.array_equal(a, np.rint(a))
+    t = ref["tower"]
+    live, distinct = float((t != 0).mean()), len(np.unique(t))
+    assert max(maxima) <= lim, ("activation beyond the exact integers of %s" % FMT[dtype]["name"], maxima)
+    assert live >= 0.40, live
+    assert distinct >= 32, distinct
+    return maxima, live, distinct
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# comparators
+# ---------------------------------------------------------------------------------------------------------------------
+def check_exact(got, ref, what=""):
+    """got: float32 from the engine; ref: float64 holding 16-bit values.  Bit for bit."""
+    got = np.ascontiguousarray(got, np.float32)
+    want = np.ascontiguousarray(ref + 0.0, np.float32)           # -0.0 + 0.0 = +0.0: the kernels' ReLU gives +0
+    assert got.shape == want.shape, (what, got.shape, want.shape)
+    bad = got.view(np.uint32) != want.view(np.uint32)
+    if bad.any():
+        idx = np.argwhere(bad)
+        raise AssertionError("%s: %d of %d elements differ; first at %s: got %r, want %r" % (
+            what, int(bad.sum()), bad.size, idx[0].tolist(), float(got[tuple(idx[0])]), float(want[tuple(idx[0])])))
+
+
+def noise_figures(a, ref, dtype):
+    """(largest distance, share of elements more than one rounding away) of a from the float64-accumulated reference,
+    in roundings of the operand type at the reference's magnitude: the quantum at max(|ref element|, rms of ref).
+    The floor is the scale of the terms an element is summed from: an output that cancels to 1e-5 still carries the
+    error of operands of magnitude rms, and measured in ITS quanta (6e-8 in fp16) one flipped rounding upstream is
+    hundreds of "roundings" -- a maximum over 10^6 such elements is a lottery between any two summation orders (measured:
+    46 960 against 22 430 for two fp32 orders of one bf16 network) and would hide a zeroed activation."""
+    ref = np.asarray(ref, np.float64)
+    d = np.abs(np.asarray(a, np.float64) - ref) / quantum(np.maximum(np.abs(ref), np.sqrt((ref * ref).mean())), dtype)
+    return float(d.max()), float((d > 1.0).mean())
+
+
+def bound_of(cpu_fig):
+    """largest distance <= max(2 roundings, 2 x the CPU figure of the same case); share of elements more
+    than one rounding away <= 2 x the CPU share"""
+    return max(2.0, 2.0 * cpu_fig[0]), 2.0 * cpu_fig[1]
+
+
+def check_bounded(got, ref, cpu_fig, dtype, what=""):
+    fig = noise_figures(got, ref, dtype)
+    lim = bound_of(cpu_fig)
+    print("%s: CPU f32 order %.2f roundings / share>1 %.3e; kernel %.2f roundings / share>1 %.3e; bounds %.2f / %.3e" % (
+        what, cpu_fig[0], cpu_fig[1], fig[0], fig[1], lim[0], lim[1]))
+    assert np.isfinite(np.asarray(got)).all(), what
+    assert fig[0] <= lim[0], (what, "largest distance", fig[0], "bound", lim[0])
+    assert fig[1] <= lim[1], (what, "share more than one rounding away", fig[1], "bound", lim[1])
+    return fig
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the Linears and the blob
+# ---------------------------------------------------------------------------------------------------------------------
+def head_len(F, nblocks):
+    """bytes of header + conv sections of a weight blob (csrc/fpc_nn.h "weight blob"; every section a multiple of 64)"""
+    Fp = (F + 127) // 128 * 128
+    return 64 + 9 * Fp * 32 * 2 + Fp * 4 + 2 * nblocks * (9 * Fp * F * 2 + Fp * 4) + 2 * (9 * 128 * F * 2 + 128 * 4)
+
+
+def value_vector(R, seed=99):
+    """the value Linear's fixed random weights [24 * R * R] (NCHW flatten) and bias"""
+    g = torch.Generator().manual_seed(seed)
+    return (torch.randn(24 * R * R, generator=g) / (24 * R * R) ** 0.5).numpy().astype(np.float32), np.float32(0.05)
+
+
+def permutation(R, seed=7):
+    """(perm, scale): row i of the permutation Linear holds scale[i] = +-2^k, k in -2..2, at column perm[i]"""
+    A = (8 * R + 8) * R * R
+    rng = np.random.default_rng(seed)
+    return rng.permutation(A), (rng.choice([-1.0, 1.0], size=A) * np.exp2(rng.integers(-2, 3, size=A))).astype(np.float32)
+
+
+class Tail:
+    """the Linear sections of an exported blob and the header words that describe them"""
+    def __init__(self, R, dtype, layout, kind):
+        A_ch, RR = 8 * R + 8, R * R
+        A = A_ch * RR
+        m = net.ResNet(stub_spec(R), 0, 64, "cpu")
+        fc = torch.nn.utils.skip_init(torch.nn.Linear, A, A)
+        with torch.no_grad():
+            fc.weight.zero_()
+            fc.bias.zero_()
+            if kind == "identity":
+                fc.weight.diagonal().fill_(1.0)
+            else:
+                perm, scale = permutation(R)
+                fc.weight[torch.arange(A), torch.from_numpy(perm)] = torch.from_numpy(scale)
+            vfc = torch.nn.Linear(24 * RR, 1)
+            vw, vb = value_vector(R)
+            vfc.weight.copy_(torch.from_numpy(vw).view(1, -1))
+            vfc.bias.fill_(float(vb))
+        m.policyHead[4], m.valueHead[4] = fc, vfc
+        blob = weights.export_weights(m.eval(), dtype, fc_layout=layout)
+        del m, fc
+        magic, version, r, F, nb, dt, a_ch, self.Np, self.Kp, lay = struct.unpack_from("<4s9i", blob, 0)
+        assert (magic, version, r, F, nb, dt, a_ch, lay) == (b"FPCW", 3, R, 64, 0, dtype, A_ch, layout)
+        self.R, self.dtype, self.layout, self.kind = R, dtype, layout, kind
+        self.bytes = blob[head_len(64, 0):]
+
+
+_tails = {}
+
+
+def tail(R, dtype, layout, kind, keep=2):
+    """one exported Linear per (board, operand type, layout, kind); of the large ones (1.1 GB each at 14x14) only the
+    last `keep` stay cached"""
+    key = (R, dtype, layout, kind)
+    if key not in _tails:
+        big = [k for k in _tails if k[0] >= 12]
+        if R >= 12 and len(big) >= keep:
+            _tails.pop(big[0])
+        _tails[key] = Tail(R, dtype, layout, kind)
+    return _tails[key]
+
+
+def splice(m, t):
+    """the blob of the network with m's convolutions (m on the stub geometry) and t's Linears"""
+    cb = weights.export_weights(m, t.dtype, fc_layout=1)
+    magic, version, r1, F, nb, dt, a_ch, _np, _kp, _lay = struct.unpack_from("<4s9i", cb, 0)
+    assert r1 == 1 and a_ch == 8 * t.R + 8 and dt == t.dtype
+    hl = head_len(F, nb)
+    return struct.pack("<4s9i24x", b"FPCW", 3, t.R, F, nb, t.dtype, a_ch, t.Np, t.Kp, t.layout) + cb[64:hl] + t.bytes
+
+
+def expected_logits(policy, kind, R):
+    """what the probe's logits must be, from the reference's policy-conv output [n, A_ch, R, R] (NCHW flatten)"""
+    flat = policy.reshape(policy.shape[0], -1)
+    if kind == "identity":
+        return flat
+    perm, scale = permutation(R)
+    return flat[:, perm] * scale.astype(np.float64)[None, :] + 0.0
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the cases of tests/test_tower_probe_gpu.py: (kernel, R, hidden, blocks, dtype, family, developer knobs, rows)
+# Family A depths: 3 blocks with fp16 operands, 2 with bf16 (integers stay below 2^11 / 2^8; test_tower_probe_cpu.py
+# asserts the conditions for every case of this table).  Family B depths: 2, 3, 10 at hidden 128 and 2, 20 at hidden 256.
+# ---------------------------------------------------------------------------------------------------------------------
+def _cases():
+    out = []
+
+    def add(kernel, R, hidden, blocks, dtype, family, knobs=None, rows=37):
+        out.append((kernel, R, hidden, blocks, dtype, family, dict(knobs or {}), rows))
+
+    def both_a(kernel, R, hidden, knobs=None):
+        add(kernel, R, hidden, 3, 1, "A", knobs)
+        add(kernel, R, hidden, 2, 0, "A", knobs)
+
+    # k_towerc: 14x14, hidden 128
+    both_a("k_towerc", 14, 128)
+    add("k_towerc", 14, 128, 3, 1, "A", None, 300)
+    both_a("k_towerc", 14, 128, {"FPC_TOWER_TAPLOOP": "0"})      # the rolled tap loop
+    add("k_towerc", 14, 128, 2, 1, "B", {"FPC_TOWER_TAPLOOP": "0"})
+    for blocks in (2, 3, 10):
+        for dtype in (1, 0):
+            add("k_towerc", 14, 128, blocks, dtype, "B")
+    # k_towerw<128>: one wave row at 8x8, two wave rows at 9..13 (3 / 4 / 5 / 6 row tiles)
+    for R in (8, 9, 10, 11, 12, 13):
+        both_a("k_towerw", R, 128)
+    add("k_towerw", 8, 128, 3, 1, "A", None, 300)
+    for R, blocks in ((8, 10), (10, 3), (13, 2)):
+        for dtype in (1, 0):
+            add("k_towerw", R, 128, blocks, dtype, "B")
+    # k_towerw<256>: R = 8..14 (4 / 6 / 7 / 8 / 9 / 11 / 13 row tiles), and two wave rows
+    for R in (8, 9, 10, 11, 12, 13, 14):
+        both_a("k_towerw", R, 256)
+    for R in (8, 14):
+        both_a("k_towerw", R, 256, {"FPC_TOWERW_ROWS": "2"})
+    add("k_towerw", 8, 256, 3, 1, "A", None, 300)
+    for R, blocks in ((8, 2), (14, 2), (14, 20)):
+        for dtype in (1, 0):
+            add("k_towerw", R, 256, blocks, dtype, "B")
+    add("k_towerw", 14, 256, 2, 1, "B", {"FPC_TOWERW_ROWS": "2"})
+    # k_conv3x3, one launch per layer: hidden 64 always, hidden 128 / 256 under FPC_NO_TOWER=1
+    for hidden, knobs in ((64, None), (128, {"FPC_NO_TOWER": "1"}), (256, {"FPC_NO_TOWER": "1"})):
+        for R in (8, 14):
+            both_a("k_conv3x3", R, hidden, knobs)
+        for dtype in (1, 0):
+            add("k_conv3x3", 14, hidden, 2, dtype, "B", knobs)
+    add("k_conv3x3", 8, 64, 3, 1, "A", None, 300)
+    # k_tower on the bordered grid: 14x14 on 8 and on 4 waves, and the sizes k_towerw took over
+    for R, knobs in ((14, {"FPC_TOWER_COMPACT": "0"}), (14, {"FPC_TOWER_COMPACT": "0", "FPC_TOWER_WAVES": "4"}),
+                     (8, {"FPC_TOWERW": "0"}), (10, {"FPC_TOWERW": "0"}), (13, {"FPC_TOWERW": "0"})):
+        both_a("k_tower", R, 128, knobs)
+    for R, knobs in ((14, {"FPC_TOWER_COMPACT": "0"}), (8, {"FPC_TOWERW": "0"})):
+        for dtype in (1, 0):
+            add("k_tower", R, 128, 2, dtype, "B", knobs)
+    add("k_tower", 8, 128, 3, 1, "A", {"FPC_TOWERW": "0"}, 300)
+    return out
+
+
+CASES = _cases()
+
+
+def case_id(c):
+    kernel, R, hidden, blocks, dtype, family, knobs, rows = c
+    return "%s-%dx%d-h%d-b%d-%s-%s-%s%d" % (kernel, R, R, hidden, blocks, FMT[dtype]["name"], family,
+                                           "".join("%s=%s-" % (k[4:].lower(), v) for k, v in sorted(knobs.items())), rows)
+
+
+_prepared = {}
+
+
+def prepare(case):
+    """everything a case needs that the GPU does not: the network, its inputs, the float64 reference and -- family B --
+    the figures of the fp32 order on the CPU; family A's conditions are asserted here.  Cases that differ only in the
+    kernel share one preparation."""
+    kernel, R, hidden, blocks, dtype, family, knobs, rows = case
+    key = (R, hidden, blocks, dtype, family, rows)
+    if key in _prepared:
+        return _prepared[key]
+    seed = 100 * R + blocks
+    x = probe_inputs(R, rows, seed=seed, density=0.25 if family == "A" else 0.1)
+    m = integer_net(R, blocks, hidden, seed) if family == "A" else dense_net(R, blocks, hidden, seed)
+    layers = conv_layers(m, dtype)
+    ref = forward(layers, x, dtype)
+    p = {"net": m, "x": x, "ref": ref}
+    if family == "A":
+        p["conditions"] = integer_conditions(ref, dtype)
+    else:
+        # the CPU figure: the noisiest of a fixed set of fp32 orders.  One order is one draw: on a shallow
+        # network the elements more than one rounding away are 0..8 of 10^6 and differ from order to order by more than the
+        # factor 2 of the bound, so networks of at most 3 blocks draw eight orders; on deeper ones the orders agree within
+        # a few per cent and three are drawn
+        vw, vb = value_vector(R)
+        # "value": the value conv's output rounded to 16 bits (k_conv3x3 + k_value_tail); "value_unrounded": not (towers)
+        vk = {"value": "vconv", "value_unrounded": "vconv_unrounded"}
+        p["ref_value"] = {k: value_of(ref[v], vw, vb) for k, v in vk.items()}
+        figs = []
+        for order in (SHALLOW_ORDERS if blocks <= 3 else BASE_ORDERS):
+            cpu = forward(layers, x, dtype, order)
+            f = {"tower": noise_figures(cpu["tower"], ref["tower"], dtype),
+                 "policy": noise_figures(cpu["policy"], ref["policy"], dtype)}
+            for k, v in vk.items():
+                f[k] = float(np.abs(value_of(cpu[v], vw, vb, "f32") - p["ref_value"][k]).max())
+            figs.append(f)
+        p["cpu_orders"] = figs
+        p["cpu"] = {"tower": tuple(max(f["tower"][i] for f in figs) for i in (0, 1)),
+                    "policy": tuple(max(f["policy"][i] for f in figs) for i in (0, 1)),
+                    "value": max(f["value"] for f in figs), "value_unrounded": max(f["value_unrounded"] for f in figs)}
+        # two roundings of the largest value-conv activation through the largest weight: the floor of the value bound
+        p["value_floor"] = 2.0 * float(quantum(ref["vconv"].max(), dtype)) * float(np.abs(vw).max())
+    if len(_prepared) >= 4:
+        _prepared.pop(next(iter(_prepared)))
+    _prepared[key] = p
+    return p
