@@ -8,7 +8,8 @@ PyTorch(-ROCm):  loss = cross_entropy(policy_logits, pi) + mse(value, z)   (alph
 
 `args` takes the reference's keys (alphazero.py:291-306): max_game_length, C, num_searches,
 num_iterations, num_games, num_parallel_games, batch_size, temperature, heuristic_weight,
-replay_buffer_capacity, validation_buffer_capacity.
+replay_buffer_capacity, validation_buffer_capacity.  Beyond the reference: reuse_tree (default False) -- self-play keeps
+the played move's subtree from ply to ply (play(); arena.py and the drop-in MCTS.search(games) never do).
 """
 import numpy as np
 import torch
@@ -40,7 +41,11 @@ class AlphaZero:
         G = int(self.args["num_parallel_games"])
         games = [self._new_game() for _ in range(G)]
         # same (rows = games x leaves_per_step, sims, dtype) request as MCTS.search makes, so the handle is not re-created under us
-        eng = az.engine(self.mcts.engine_rows(G), int(self.args["num_searches"]), self.mcts.nn_dtype if self.mcts._native else None)
+        # args["reuse_tree"] (opt-in, default off; not reference semantics): every ply after the first continues on the
+        # subtree of the move played (MCTS.continue_search) -- with the internal network or an external evaluator alike.
+        # The handle then holds 2 * num_searches simulations: the visits kept from the last ply count against max_sims
+        reuse = bool(self.args.get("reuse_tree", False)) if hasattr(self.args, "get") else False
+        eng = az.engine(self.mcts.engine_rows(G), int(self.args["num_searches"]) * (2 if reuse else 1), self.mcts.nn_dtype if self.mcts._native else None)
         L = int(self.args["max_game_length"])
         uniforms = torch.rand(L, G, generator=self.gen, dtype=torch.float64).tolist()
 
@@ -56,7 +61,10 @@ class AlphaZero:
                 res["visits"][i, :len(v)] = v
             return res
 
-        episodes = selfplay.play(search_fn, eng, [g._b for g in games], self.args, uniforms)
+        def continue_fn(keep_idx, picks, pods):
+            return self.mcts.continue_search(pods, keep_idx, picks)
+
+        episodes = selfplay.play(search_fn, eng, [g._b for g in games], self.args, uniforms, continue_fn=continue_fn if reuse else None)
         split = self.args["replay_buffer_capacity"] / (self.args["replay_buffer_capacity"] + self.args["validation_buffer_capacity"])
         for ep in episodes:                               # handle_terminal_state, alphazero.py:53-78
             for (pod, flats, visits), z in zip(ep.entries, ep.z):

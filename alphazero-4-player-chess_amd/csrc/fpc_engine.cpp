@@ -68,6 +68,10 @@ struct fpc_engine {
   bool multi = false;             // this search runs the leaf-parallel kernels (leaves > 1 at begin, or set during it)
   int rows_k = 1;                 // leaves per game of the selection waiting to be expanded (rows = rows_k * G)
   bool pending_vl = false;        // that selection was made by a leaf-parallel kernel: its paths hold pending visits
+  // ---- subtree reuse (fpc_search_advance)
+  Tree t2{};                      // the second set of node arrays + board pool (only those nine members): k_tree_advance writes
+                                  // the re-rooted trees there and the host swaps the two sets; allocated on the first advance
+  int *d_adv = nullptr;           // [2][max_games] src_game | flat of one advance
   // ---- training tuples (device resident until the episode ends) and their RCCL exchange
   fpc_tuple *d_tuples = nullptr;
   int tuple_cap = 0, tuple_count = 0;
@@ -790,6 +794,58 @@ int fpc_search_grandchildren(fpc_engine *e, int game, int child_idx, int max_chi
   if (visits) HIPCHK(e, hipMemcpy(visits, e->t.N + nb + g0, (size_t)k * sizeof(int), hipMemcpyDeviceToHost));
   if (flat) for (int i = 0; i < k; ++i) flat[i] = mv[i];
   return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Subtree reuse: the finished search becomes the start of the next one.  k_tree_advance writes the re-rooted trees into
+// the second set of tree arrays (games move to lower indices while other blocks still read the old regions), the host
+// swaps the two sets, reads the kept root visit counts back and counts max(kept) - 1 simulations as issued: a node
+// created with N = 1 and now at N = n has had n - 1 simulations through it, which is the accounting of a fresh root
+// after n - 1 simulations for the log table, the board pool and the node pool, so admit() holds as it is.
+int fpc_search_advance(fpc_engine *e, const int *src_game, const int *flat, int n_games, fpc_board *roots_out, int *kept_visits) {
+  if (!e || !flat) return fail(e, FPC_EINVAL, "bad argument");
+  if (!e->searching || e->stepping) return fail(e, FPC_ESTATE, "fpc_search_advance needs a finished search: fpc_search_results has not been read");
+  USE_DEV(e);
+  if (n_games < 1) return fail(e, FPC_EINVAL, "n_games must be positive");
+  if (!src_game && n_games > e->G) return fail(e, FPC_EINVAL, "n_games %d > the %d games of the finished search", n_games, e->G);
+  for (int i = 0; src_game && i < n_games; ++i)
+    if (src_game[i] < 0 || src_game[i] >= e->G || (i > 0 && src_game[i] <= src_game[i - 1]))
+      return fail(e, FPC_EINVAL, "src_game must be strictly ascending within 0..%d (entry %d is %d)", e->G - 1, i, src_game[i]);
+  int r;
+  if ((r = check_rows(e, e->leaves, n_games))) return r;
+  if (e->t.noise && e->noise_n != n_games)
+    return fail(e, FPC_EINVAL, "root noise was uploaded for %d games, this search has %d: call fpc_search_set_root_noise again (or with NULL)", e->noise_n, n_games);
+  Tree &t = e->t, &u = e->t2;
+  const size_t nn = (size_t)e->cfg.max_games * t.node_cap;
+  if ((!u.N && (r = dalloc(e, &u.N, nn))) || (!u.W && (r = dalloc(e, &u.W, nn))) || (!u.P && (r = dalloc(e, &u.P, nn))) ||
+      (!u.mv && (r = dalloc(e, &u.mv, nn))) || (!u.parent && (r = dalloc(e, &u.parent, nn))) || (!u.child0 && (r = dalloc(e, &u.child0, nn))) ||
+      (!u.nch && (r = dalloc(e, &u.nch, nn))) || (!u.bslot && (r = dalloc(e, &u.bslot, nn))) ||
+      (!u.boards && (r = dalloc(e, &u.boards, (size_t)e->cfg.max_games * t.board_cap))) ||
+      (!e->d_adv && (r = dalloc(e, &e->d_adv, (size_t)2 * e->cfg.max_games))))
+    return r;
+  int *d_src = e->d_adv, *d_flat = e->d_adv + e->cfg.max_games;
+  if (src_game) HIPCHK(e, hipMemcpyAsync(d_src, src_game, (size_t)n_games * sizeof(int), hipMemcpyHostToDevice, e->stream));
+  HIPCHK(e, hipMemcpyAsync(d_flat, flat, (size_t)n_games * sizeof(int), hipMemcpyHostToDevice, e->stream));
+  Tree o = t;
+  o.N = u.N; o.W = u.W; o.P = u.P; o.mv = u.mv; o.parent = u.parent; o.child0 = u.child0; o.nch = u.nch; o.bslot = u.bslot; o.boards = u.boards;
+  FPC_LAUNCH(k_tree_advance, n_games, 64, e->stream, e->dc, t, o, n_games, src_game ? (const int *)d_src : (const int *)nullptr,
+             (const int *)d_flat, e->d_VL, e->d_rc_meta, e->d_roots);
+  HIPCHK(e, hipGetLastError());
+  std::swap(t.N, u.N); std::swap(t.W, u.W); std::swap(t.P, u.P); std::swap(t.mv, u.mv); std::swap(t.parent, u.parent);
+  std::swap(t.child0, u.child0); std::swap(t.nch, u.nch); std::swap(t.bslot, u.bslot); std::swap(t.boards, u.boards);
+  e->G = n_games;
+  e->stepping = true;
+  e->multi = e->leaves > 1;
+  e->rows_k = 1;
+  e->pending_vl = false;
+  std::vector<int> kept(n_games), errs(n_games);
+  HIPCHK(e, hipMemcpyAsync(kept.data(), e->d_rc_meta, (size_t)n_games * sizeof(int), hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(e, hipMemcpyAsync(errs.data(), t.err, (size_t)n_games * sizeof(int), hipMemcpyDeviceToHost, e->stream));
+  if (roots_out) HIPCHK(e, hipMemcpyAsync(roots_out, e->d_roots, (size_t)n_games * sizeof(fpc_board), hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(e, hipStreamSynchronize(e->stream));
+  e->sims_issued = (long)*std::max_element(kept.begin(), kept.end()) - 1;
+  if (kept_visits) std::copy(kept.begin(), kept.end(), kept_visits);
+  return err_to_status(e, errs, "game");
 }
 
 // ------------------------------------------------------------------------------------------------

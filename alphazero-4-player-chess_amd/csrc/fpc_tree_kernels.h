@@ -13,6 +13,7 @@
 //   k_expand_select  k_expand of simulation step s + k_select of step s+1 in one launch
 //   k_select_multi / k_expand(_legal)(_select)_multi  the same for the opt-in leaf-parallel search (K leaves per game
 //                    per step, virtual loss; fpc_search_set_leaves): the descent is select_game's, row k*G + g per leaf
+//   k_tree_advance   opt-in subtree reuse (fpc_search_advance): re-roots every game's tree on the move played, out of place
 //
 // Reference semantics (file:line relative to /root/reference/src/cpp) are restated per function.
 // Nothing here is translated from the reference: its board is a pointer-rich mailbox + std::vector
@@ -249,9 +250,10 @@ __device__ __forceinline__ int wave_list_erase_append(uint8_t *list, int len, in
 // mover's castling rights and a rook leaving its home square clears that side's.
 // Wave-cooperative and wave-uniform: every lane derives the same scalars from the LDS board, the piece
 // lists are edited one entry per lane, lane 0 writes the scalars.  All lanes must call.
-// LEAF_PARALLEL: a separate instance for the leaf-parallel selection, so that the one-leaf kernels' callees -- and with
-// them the compiler's inlining decisions and the kernels' ISA -- stay exactly what they were before leaf-parallel search
-template <bool LEAF_PARALLEL = false>
+// INSTANCE: 0 the one-leaf kernels, 1 (LEAF_PARALLEL) the leaf-parallel selection, 2 k_tree_advance -- separate
+// instances, so that the one-leaf kernels' callees -- and with them the compiler's inlining decisions and the kernels'
+// ISA -- stay exactly what they were before leaf-parallel search and subtree reuse
+template <int INSTANCE = 0>
 __device__ inline bool make_move_wave(fpc_board *b, int from, int to, const DevCfg &c) {
   const int lane = lane_id();
   if (to == FPC_NO_SQ) return false;
@@ -1871,6 +1873,153 @@ __global__ void __launch_bounds__(64) k_expand_legal_select_multi(DevCfg c, Tree
   if (g >= G) return;
   expand_game_multi<true>(s, c, t, G, g, kexp, LogitSrc{}, ll, nullptr, value, lp.VL);
   select_game_multi(s, c, t, G, g, ksel, Cpuct, logtab, true, lp);
+}
+
+// ================================================================================================
+// k_tree_advance (fpc_search_advance, opt-in subtree reuse; not reference semantics -- the reference builds a fresh
+// tree per ply): new game g continues old game src_game[g] from the root child whose move is flat[g].  That child
+// becomes node 0 (parent -1, move 0xffff, N / W kept), its subtree follows with N, W, P, move, the children's order
+// and every materialised board; the rest of the old tree is dropped.
+//
+// OUT OF PLACE: games move to lower indices and the blocks run concurrently, so block g would overwrite a region that
+// another block is still reading.  `t` is the finished search (read only, apart from the per-game scalars, which no
+// block reads), `o` the same Tree with the eight node arrays and the board pool replaced by the second set; the host
+// swaps the two sets after the launch.
+//
+// Breadth-first append, one wave per game: new node j keeps its OLD (child0, nch) until it is processed.  64 queue
+// entries at a time: a wave scan of their child counts places every entry's child block at the tail (blocks stay
+// contiguous, children keep their order); the blocks are then copied as ONE flat range, 64 nodes per pass with
+// coalesced stores, each lane finding its queue entry by bisection of the scanned offsets; the materialised nodes of a
+// pass get consecutive new board slots (ballot prefix) and their 288-byte states are copied as one flat range of
+// dwords.  No mark array, no atomics, and the node order is a function of the old tree alone.
+// The new root's state is board slot 0: the child's board, or -- a child that was never selected (Q1: every child has
+// N = 1, so a sampled move can be one) -- the old root's board with the move made, which is what a selection would
+// have done, and no more (no GetGameResult / legal-moves pass).
+// Root noise: a new root that is already expanded gets it here, child i (ascending flat order) from gamma[g][i], with
+// expand_finish's operations in expand_finish's order; an unexpanded one gets it when it is expanded (n == 0).
+// ================================================================================================
+__global__ void __launch_bounds__(64) k_tree_advance(DevCfg c, Tree t, Tree o, int G, const int *src_game, const int *flat, int *VL,
+                                                     int *kept, fpc_board *roots_out) {
+  __shared__ WaveLds s;
+  __shared__ int q_c0[64], q_ex[64], q_bs[64];
+  const int g = blockIdx.x;
+  if (g >= G) return;
+  const int lane = lane_id();
+  const int sg = src_game ? src_game[g] : g, fl = flat[g];
+  const size_t ob = (size_t)sg * t.node_cap, nb = (size_t)g * t.node_cap;
+  const fpc_board *opool = t.boards + (size_t)sg * t.board_cap;
+  fpc_board *npool = o.boards + (size_t)g * t.board_cap;
+  // ---- the root child that was played
+  const int rc0 = t.child0[ob], rnc = rc0 < 0 ? 0 : (int)t.nch[ob];
+  int r = -1;
+  for (int base = 0; base < rnc && r < 0; base += 64) {
+    const int i = base + lane;
+    const unsigned long long hit = __ballot(i < rnc && (int)t.mv[ob + rc0 + i] == fl);
+    if (hit) r = rc0 + base + (int)__ffsll((long long)hit) - 1;
+  }
+  int errbits = r < 0 ? ERR_MOVE : 0;      // not a root child: the game is killed with a childless root on the old root's state
+  const int rslot = r < 0 ? 0 : t.bslot[ob + r], rootN = r < 0 ? 1 : t.N[ob + r];
+  if (lane == 0) {
+    o.N[nb] = rootN; o.W[nb] = r < 0 ? 0.0 : t.W[ob + r]; o.P[nb] = r < 0 ? 0.f : t.P[ob + r]; o.mv[nb] = 0xffff; o.parent[nb] = -1;
+    o.child0[nb] = r < 0 ? -1 : t.child0[ob + r]; o.nch[nb] = r < 0 ? (uint16_t)0 : t.nch[ob + r]; o.bslot[nb] = 0;
+  }
+  // ---- its state -> board slot 0 (the root of a tree is always in slot 0)
+  if (rslot < 0) {
+    lds_load_board(&s, &opool[0]);
+    int from;
+    const int to = flat_to(c, fl, &from);
+    if (!make_move_wave<2>(&s.b, from, to, c)) errbits |= ERR_MOVE;
+    lds_store_board(&s, &npool[0]);
+  } else {
+    const uint32_t *src = reinterpret_cast<const uint32_t *>(&opool[rslot]);
+    uint32_t *dst = reinterpret_cast<uint32_t *>(&npool[0]);
+    dst[lane] = src[lane];
+    if (lane < 8) dst[64 + lane] = src[64 + lane];
+  }
+  __syncthreads();
+  // ---- breadth-first append of the subtree
+  int tail = 1, nbo = 1;
+  for (int head = 0, end = 1; head < tail && !(errbits & (ERR_CAP_NODES | ERR_CAP_BOARDS)); head = end) {
+    end = head + 64 < tail ? head + 64 : tail;              // this batch: queue entries head .. end-1
+    const int j = head + lane;
+    int oc0 = -1, cnt = 0;
+    if (j < end) { oc0 = o.child0[nb + j]; cnt = oc0 < 0 ? 0 : (int)o.nch[nb + j]; }
+    int inc = cnt;                                          // inclusive scan of the child counts
+    for (int d = 1; d < 64; d <<= 1) {
+      const int v = __shfl_up(inc, d);
+      if (lane >= d) inc += v;
+    }
+    const int total = wave_read(inc, 63), ex = inc - cnt;
+    if (tail + total > t.node_cap) { errbits |= ERR_CAP_NODES; break; }     // cannot happen: a subtree of a tree that fitted
+    if (oc0 >= 0) o.child0[nb + j] = tail + ex;
+    q_c0[lane] = oc0; q_ex[lane] = ex;                      // lanes past the batch: ex == total, never found
+    __syncthreads();
+    for (int p0 = 0; p0 < total; p0 += 64) {
+      const int p = p0 + lane;
+      const bool in = p < total;
+      int bs = -1;
+      size_t dn = 0;
+      if (in) {
+        int en = 0;                                         // the last entry with ex <= p: the one whose block holds p
+        for (int step = 32; step; step >>= 1) if (q_ex[en + step] <= p) en += step;
+        const size_t so = ob + q_c0[en] + (p - q_ex[en]);
+        dn = nb + tail + p;
+        o.N[dn] = t.N[so]; o.W[dn] = t.W[so]; o.P[dn] = t.P[so]; o.mv[dn] = t.mv[so]; o.parent[dn] = head + en;
+        o.child0[dn] = t.child0[so]; o.nch[dn] = t.nch[so];
+        bs = t.bslot[so];
+      }
+      const unsigned long long mat = __ballot(bs >= 0);
+      const int m = __popcll(mat), mi = __popcll(mat & ((1ull << lane) - 1ull));
+      if (nbo + m > t.board_cap) { errbits |= ERR_CAP_BOARDS; break; }      // cannot happen either
+      if (in) o.bslot[dn] = bs >= 0 ? nbo + mi : -1;
+      if (m) {                                              // wave-uniform
+        if (bs >= 0) q_bs[mi] = bs;
+        __syncthreads();
+        for (int q = lane; q < m * 72; q += 64) {           // 72 dwords per state
+          const int bi = q / 72, w = q - bi * 72;
+          reinterpret_cast<uint32_t *>(&npool[nbo + bi])[w] = reinterpret_cast<const uint32_t *>(&opool[q_bs[bi]])[w];
+        }
+        nbo += m;
+        __syncthreads();
+      }
+    }
+    tail += total;
+    __syncthreads();                                        // this batch's stores precede the next batch's loads; q_* are reused
+  }
+  if (errbits & (ERR_CAP_NODES | ERR_CAP_BOARDS)) {         // leave a childless root rather than a half-built tree
+    __syncthreads();
+    if (lane == 0) { o.child0[nb] = -1; o.nch[nb] = 0; }
+    tail = 1; nbo = 1;
+    __syncthreads();
+  }
+  // ---- root noise on an expanded new root (its children are nodes 1 .. nch)
+  const int nc = o.child0[nb] < 0 ? 0 : (int)o.nch[nb];
+  if (t.noise != nullptr && nc > 0 && !errbits) {
+    const float *gm = t.noise + (size_t)g * FPC_MAX_MOVES;
+    const int nn = nc < FPC_MAX_MOVES ? nc : FPC_MAX_MOVES;
+    if (lane == 0) {
+      float sgm = 0.f;
+      for (int k = 0; k < nn; ++k) sgm = sgm + gm[k];
+      s.scal_f = sgm;
+    }
+    __syncthreads();
+    const float SG = s.scal_f;
+    if (SG > 0.f)
+      for (int k = lane; k < nn; k += 64) o.P[nb + 1 + k] = (1.0f - t.noise_eps) * o.P[nb + 1 + k] + t.noise_eps * fdiv_rn(gm[k], SG);
+  }
+  if (VL != nullptr)                                         // no pending visit survives from the game that lived in this region
+    for (int k = lane; k < tail; k += 64) VL[nb + k] = 0;
+  {
+    const uint32_t *src = reinterpret_cast<const uint32_t *>(&npool[0]);
+    uint32_t *dst = reinterpret_cast<uint32_t *>(&roots_out[g]);
+    dst[lane] = src[lane];
+    if (lane < 8) dst[64 + lane] = src[64 + lane];
+  }
+  if (lane == 0) {
+    t.nnodes[g] = tail; t.nboards[g] = nbo; t.alive[g] = errbits ? 0 : 1; t.sims_done[g] = 0; t.err[g] = errbits;
+    t.leaf_node[g] = -1; t.leaf_slot[g] = -1; t.leaf_turn[g] = 0; t.nlegal[g] = 0;
+    kept[g] = rootN;
+  }
 }
 
 }  // namespace fpc

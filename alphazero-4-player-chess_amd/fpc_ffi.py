@@ -121,6 +121,7 @@ _SIGS = {
     "fpc_search_run": (C.c_int, [C.c_void_p, C.c_int]),
     "fpc_search_results": (C.c_int, [C.c_void_p, P(Board), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
                                      C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fpc_search_advance": (C.c_int, [C.c_void_p, P(C.c_int), P(C.c_int), C.c_int, P(Board), P(C.c_int)]),
     "fpc_search_grandchildren": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, P(C.c_int), C.c_void_p, C.c_void_p]),
     "fpc_load_weights": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
     "fpc_nn_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
@@ -357,6 +358,31 @@ class Engine:
                 C.memmove(C.byref(b), pods[g].ctypes.data, BOARD_BYTES)
         return {"root_n": rv, "n_children": nc, "sims_done": sd, "flat": cf, "visits": cv, "prior": cp, "w": cw,
                 "boards": _LazyBoards(pods)}
+
+    def search_advance(self, flats, src_games=None, roots=None, roots_np=None):
+        """subtree reuse (include/fpc_engine.h fpc_search_advance): re-root the finished search; new game i continues old
+        game src_games[i] (None: game i) from the root child whose move is flats[i].  roots: list of Board, roots_np:
+        [n, 288] uint8 array, to receive the new root PODs.  Returns the new roots' visit counts (int32 [n]); continue
+        with search_run / the step entry points and search_results."""
+        fl = np.ascontiguousarray(flats, np.int32)
+        n = int(fl.shape[0])
+        sg = None
+        if src_games is not None:
+            sa = np.ascontiguousarray(src_games, np.int32)
+            assert sa.shape == (n,)
+            sg = C.cast(sa.ctypes.data, P(C.c_int))
+        pods = np.zeros((n, BOARD_BYTES), np.uint8) if roots_np is None else roots_np
+        assert pods.shape == (n, BOARD_BYTES) and pods.dtype == np.uint8 and pods.flags.c_contiguous
+        kept = np.zeros(n, np.int32)
+        rc = self.L.fpc_search_advance(self.h, sg, C.cast(fl.ctypes.data, P(C.c_int)), n, _bp(pods) if n else None,
+                                       C.cast(kept.ctypes.data, P(C.c_int)))
+        if rc == 0 or rc == -7:           # FPC_EMOVE: the other games were advanced
+            self.G = n
+        self._chk(rc)
+        if roots is not None:
+            for g, b in enumerate(roots):
+                C.memmove(C.byref(b), pods[g].ctypes.data, BOARD_BYTES)
+        return kept
 
     # ---- the same position ops on [n, 288] uint8 arrays of PODs (callers that keep a whole batch in one array:
     #      bench.py's per-ply host section, mcts.py's root-children prefetch) ----

@@ -120,6 +120,34 @@ class MCTS:
         assert int(res["n_children"].min()) > 0         # mcts.py:40-41
         return roots
 
+    @torch.no_grad()
+    def continue_search(self, pods, keep_idx, flats):
+        """Opt-in subtree reuse (not reference semantics; include/fpc_engine.h fpc_search_advance), for callers that know
+        the moves played -- selfplay.play(continue_fn=...); the drop-in search(games) carries no move history and always
+        starts fresh trees.  Re-roots the search this object ran last: new game i continues game keep_idx[i] of it from
+        the root child flats[i], then runs num_searches simulations on the kept subtrees -- fewer where kept + new would
+        pass the engine's max_sims (create the engine with 2 * num_searches, as AlphaZero.play does).  `pods` (list of
+        fpc_ffi.Board) receive the new root states.  Returns the fpc_ffi.Engine.search_results dict."""
+        G = len(flats)
+        eng = az.engine()
+        eng.set_rules(int(self.rules))
+        eng.set_leaves(self.leaves, self.virtual_loss)
+        if self.root_noise:
+            import fpc_ffi
+            gamma = self._noise_rng.standard_gamma(float(self.args["dirichlet_alpha"]), size=(G, fpc_ffi.MAX_MOVES)).astype(np.float32)
+            eng.set_root_noise(gamma, float(self.args["dirichlet_epsilon"]))
+        else:
+            eng.set_root_noise(None, 0.0)
+        kept = eng.search_advance(flats, keep_idx, roots=pods)
+        sims = min(int(self.args["num_searches"]), eng.max_sims - (int(kept.max()) - 1))
+        if self._native:
+            self.sync_weights(eng)
+            eng.set_policy_mode(self.policy_head == "legal")
+            eng.search_run(sims)
+        else:
+            self._search_external(eng, G, sims)
+        return eng.search_results(roots=pods)
+
     def _search_external(self, eng, G, sims):
         dev = str(getattr(self.neural_net, "device", "cpu"))
         on_gpu = dev.startswith("cuda") or dev == "gpu"

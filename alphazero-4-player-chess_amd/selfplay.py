@@ -42,9 +42,14 @@ class Episode:
         self.length = 0
 
 
-def play(search_fn, eng, start_boards, args, uniforms):
+def play(search_fn, eng, start_boards, args, uniforms, continue_fn=None):
     """search_fn(list_of_PODs) -> search_results dict (fpc_ffi.Engine.search_results layout) and
     leaves the PODs with the piece-list order the search produced.  uniforms[ply][gid] in [0,1).
+    continue_fn (opt-in subtree reuse, not reference semantics; None: every ply is search_fn, as in the reference):
+    from the second ply on the loop calls continue_fn(keep_idx, picks_of_kept, states) instead -- keep_idx: the
+    indices, within the last batch, of the games that go on (ascending), picks_of_kept: the moves they played; it
+    re-roots the last search on those moves (fpc_search_advance), searches, overwrites `states` with the trees' root
+    PODs and returns the same dict.  Terminal detection stays here, on this loop's own copies of the states.
     Returns the list of finished Episodes (all games, in game-id order)."""
     R = eng.R
     states = [fpc_ffi.clone_board(b) for b in start_boards]
@@ -54,7 +59,7 @@ def play(search_fn, eng, start_boards, args, uniforms):
     for ply in range(int(args["max_game_length"])):
         if not states:
             break
-        res = search_fn(states)
+        res = search_fn(states) if continue_fn is None or ply == 0 else continue_fn(keep_pos, keep_picks, states)
         picks = []
         for i in range(len(states)):
             n = int(res["n_children"][i])
@@ -63,7 +68,7 @@ def play(search_fn, eng, start_boards, args, uniforms):
             picks.append(sample_action(flats, visits, T, uniforms[ply][ids[i]]))
         nxt = eng.take_action(states, picks)
         results = eng.game_result(nxt)
-        keep_s, keep_i = [], []
+        keep_s, keep_i, keep_pos, keep_picks = [], [], [], []
         for i in range(len(states)):
             e = eps[ids[i]]
             e.moves.append(picks[i])
@@ -73,7 +78,7 @@ def play(search_fn, eng, start_boards, args, uniforms):
                 losing_team = states[i].turn & 1               # team of the player who just moved (Q12)
                 e.z = [1.0 if (b.turn & 1) != losing_team else -1.0 for b, _, _ in e.entries]
             else:
-                keep_s.append(nxt[i]); keep_i.append(ids[i])
+                keep_s.append(nxt[i]); keep_i.append(ids[i]); keep_pos.append(i); keep_picks.append(picks[i])
         states, ids = keep_s, keep_i
     for s, g in zip(states, ids):                                # max_game_length reached (:161-175)
         e = eps[g]

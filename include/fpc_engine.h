@@ -187,6 +187,30 @@ int fpc_search_set_root_noise(fpc_engine *e, const float *gamma, int n_games, fl
 #define FPC_MAX_LEAVES 8
 int fpc_search_set_leaves(fpc_engine *e, int leaves, double virtual_loss);
 
+/* ---- subtree reuse (opt-in, held against a model of these semantics, not against the reference, which builds a fresh
+ * tree for every ply) ---------------------------------------------------------------------------------------------
+ * Re-roots the FINISHED search (fpc_search_results has been read; otherwise FPC_ESTATE) on the moves played: new game i
+ * continues old game src_game[i] (NULL: game i) from the root child whose move is flat[i], and the engine is then in the
+ * state fpc_search_begin leaves it in, with G = n_games: fpc_search_run or the step entry points continue the search.
+ * The child becomes the root (its N and W as they are) and keeps its whole subtree -- N, W, P, moves, the children's
+ * order, every materialised state; the rest of the old tree is dropped.  The new root's state is made from the old
+ * root's by the move if the child was never selected (every child starts with N = 1, Q1), without a GetGameResult /
+ * legal-moves pass.  Per game: alive, no error, sims_done = 0.
+ * Budget: a root kept with N = n has had n - 1 simulations through it, so the call counts max_i(kept_visits[i]) - 1
+ * simulations as issued; kept + new simulations beyond max_sims give FPC_ECAPACITY as after fpc_search_begin (create the
+ * engine with max_sims = 2 x the per-ply simulations to be safe).
+ * Root noise, if set: applied here to the children of an already expanded new root (child i, in ascending flat
+ * order, takes the i-th draw of its game's row; the arithmetic of the expansion); an unexpanded root gets it when it is expanded.
+ * Leaf-parallel: no pending visit survives.  The work is done out of place (games move to lower indices): the first call
+ * allocates a second set of tree arrays and a second board pool (FPC_ENOMEM if that fails).
+ * FPC_EINVAL: src_game not strictly ascending within 0..G-1 (ascending keeps the reference's delete-from-the-list
+ * batch order, which the batch-wide rotation Q6 depends on), n_games < 1, leaves * n_games > max_games, root noise set
+ * for another number of games.  A flat[i] that is no root child of src_game[i] kills that game with its error set, and
+ * the call returns FPC_EMOVE after advancing the others.
+ * roots_out (nullable): the new root states; kept_visits (nullable): the new roots' visit counts. */
+int fpc_search_advance(fpc_engine *e, const int *src_game /* nullable: 0..n_games-1 */, const int *flat,
+                       int n_games, fpc_board *roots_out /* nullable */, int *kept_visits /* nullable */);
+
 /* Root read-back == what alphazero.py:104-110 reads through Node.GetChildren /
  * GetMoveMade().GetFlatIndex() / GetVisitCount().  Arrays are [n_games][max_children].
  * roots_out (nullable): the root states with the piece-list order the search left them in. */
