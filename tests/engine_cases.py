@@ -6,7 +6,7 @@ import numpy as np
 
 import evaluators
 import fpc_ffi
-from fpc_testlib import expand_promos, gold, make_engine, run_external_search
+from fpc_testlib import expand_promos, gold, make_engine, roots_of, run_external_search
 from oracle import orc
 
 
@@ -175,6 +175,8 @@ def case_search_random_vs_oracle(backend, R, n_games, sims, seed, kind="hash"):
         if orc.game_result(orc.clone(b), R, INV) != 0:
             b = orc.board_from_dict(R, st["turn"], st["dict"])
         roots_o.append(b)
+    # not roots_of: as through the reference's boundary, which drops castling rights (Q10), the POD is made from the
+    # lists alone -- these games start without rights, so there are none to copy
     roots = [fpc_ffi.board_from_lists(R, b.turn, orc.lists_of(b)) for b in roots_o]
     ev = evaluators.make(kind, R)
     rc, oref = orc.search([orc.clone(b) for b in roots_o], R, INV, sims, 3.0, ev)
@@ -279,7 +281,7 @@ def case_other_sizes_vs_oracle(backend, R, INV, n_games=6, sims=40, seed=5):
     ev = evaluators.make("hash", R)
     rc, oref = orc.search([orc.clone(b) for b in roots_o], R, INV, sims, 3.0, ev)
     assert rc == 0
-    roots = [fpc_ffi.board_from_lists(R, b.turn, orc.lists_of(b)) for b in roots_o]
+    roots = [fpc_ffi.board_from_lists(R, b.turn, orc.lists_of(b)) for b in roots_o]      # no rights in these games
     res = run_external_search(eng, backend, roots, sims, 3.0, ev)
     _compare_search(res, oref, ("size", R))
     eng.close()
@@ -327,12 +329,7 @@ def case_castling_vs_oracle(backend, n_games=4, plies=40, sims=30, seed=21):
     ev = evaluators.make("hash", R)
     rc, oref = orc.search([orc.clone(b) for b in roots_o], R, INV, sims, 3.0, ev)
     assert rc == 0
-    roots = []
-    for b in roots_o:
-        fb = fpc_ffi.board_from_lists(R, b.turn, orc.lists_of(b))
-        for c in range(4):
-            fb.castle[c] = b.castle[c]
-        roots.append(fb)
+    roots = roots_of(roots_o, R)
     res = run_external_search(eng, backend, roots, sims, 3.0, ev)
     _compare_search(res, oref, ("castling",))
     eng.close()
@@ -398,7 +395,7 @@ def case_arena_vs_oracle(backend, R, n_pairs=3, sims=24, max_len=30, seed=9, kin
 
     # ---- the engine's arena
     eng = make_engine(backend, R, INV, max_games=2 * n_pairs, max_sims=sims)
-    starts = [fpc_ffi.board_from_lists(R, b.turn, orc.lists_of(b)) for b in starts_o]
+    starts = [fpc_ffi.board_from_lists(R, b.turn, orc.lists_of(b)) for b in starts_o]    # no rights in these games
     games = arena.play_paired(lambda pods: run_external_search(eng, backend, pods, sims, 3.0, ev_a),
                               lambda pods: run_external_search(eng, backend, pods, sims, 3.0, ev_b), eng, starts, args)
     assert len(games) == len(ogames)
@@ -471,12 +468,7 @@ def case_fixed_rules_vs_oracle(backend, R, n_games=6, plies=60, sims=40, seed=31
             eng.set_root_noise(gamma, 0.25)
         rc, oref = orc.search([orc.clone(b) for b in roots_o], R, INV, sims, 3.0, ev)
         assert rc == 0
-        roots = []
-        for b in roots_o:
-            fb = fpc_ffi.board_from_lists(R, b.turn, orc.lists_of(b))
-            for c in range(4):
-                fb.castle[c] = b.castle[c]
-            roots.append(fb)
+        roots = roots_of(roots_o, R)
         res = run_external_search(eng, backend, roots, sims, 3.0, ev, fused=True)
         _compare_search(res, oref, ("fixed", R, rules))
         if noise:      # the noise really entered: strict-rule priors differ

@@ -52,48 +52,65 @@ class DevPtr:
                                          "version": 2}
 
 
-def run_external_search(eng, backend, roots, sims, c_puct, evaluator, fused=False):
-    """Drives fpc_search_select / evaluator / fpc_search_expand exactly like mcts.py:36-38 does.
-    evaluator: numpy callable(enc[G,24,R,R]) -> (logits[G,A], value[G]).
-    fused: between two evaluations use fpc_search_expand_select (one launch) instead of expand + select."""
-    G, R, A = len(roots), eng.R, eng.A
-    eng.search_begin(roots, c_puct)
-    keep = []
-    n_live, enc_ptr = eng.search_select() if sims > 0 else (0, None)
-    for i in range(sims):
-        last = i == sims - 1
+def run_schedule(eng, backend, sched, evaluator, fused, set_leaves=None):
+    """The select / evaluator / expand loop over the search in progress, driven like mcts.py:36-38 does: one step per
+    entry of `sched`, the step's leaves per game (its rows are [k*G, 24, R, R]).
+    evaluator: numpy callable(enc[rows,24,R,R]) -> (logits[rows,A], value[rows]).
+    fused: between two evaluations use fpc_search_expand_select (one launch) instead of expand + select.
+    set_leaves: callable(k) that sets the engine's leaves per step, called with the NEXT step's count before that
+    step's selection (the first step's count is the caller's to set); None: `sched` is all ones and the engine's
+    setting is left alone."""
+    G, R = eng.G, eng.R
+    n_live, enc_ptr = eng.search_select() if sched else (0, None)
+    for s, k in enumerate(sched):
+        last = s == len(sched) - 1
+        if set_leaves is not None and not last:
+            set_leaves(sched[s + 1])
         if n_live == 0:
             if not last:
                 n_live, enc_ptr = eng.search_select()
             continue
         if backend == "emul":
-            enc = np.ctypeslib.as_array(C.cast(enc_ptr, C.POINTER(C.c_float)), shape=(G, 24, R, R))
-            lg, v = evaluator(enc)
+            enc = np.ctypeslib.as_array(C.cast(enc_ptr, C.POINTER(C.c_float)), shape=(k * G, 24, R, R))
+            lg, v = evaluator(enc.copy())
             lg = np.ascontiguousarray(lg, dtype=np.float32)
             v = np.ascontiguousarray(v, dtype=np.float32)
-            keep = [lg, v]
             lp, vp = lg.ctypes.data, v.ctypes.data
         else:
             import torch
-            enc_t = torch.as_tensor(DevPtr(enc_ptr, (G, 24, R, R)), device="cuda")
-            enc = enc_t.cpu().numpy()
+            enc = torch.as_tensor(DevPtr(enc_ptr, (k * G, 24, R, R)), device="cuda").cpu().numpy()
             lg, v = evaluator(enc)
-            lg_t = torch.from_numpy(np.ascontiguousarray(lg, dtype=np.float32)).cuda()
-            v_t = torch.from_numpy(np.ascontiguousarray(v, dtype=np.float32)).cuda()
+            lg = torch.from_numpy(np.ascontiguousarray(lg, dtype=np.float32)).cuda()
+            v = torch.from_numpy(np.ascontiguousarray(v, dtype=np.float32)).cuda()
             torch.cuda.synchronize()
-            keep = [lg_t, v_t]
-            lp, vp = lg_t.data_ptr(), v_t.data_ptr()
-        if fused and not last:
+            lp, vp = lg.data_ptr(), v.data_ptr()
+        if fused and not last:                       # lg, v stay alive through the calls that read them
             n_live, enc_ptr = eng.search_expand_select(lp, vp)
         else:
             eng.search_expand(lp, vp)
             if not last:
                 n_live, enc_ptr = eng.search_select()
         if backend != "emul":
-            import torch
             torch.cuda.synchronize()
-    del keep
+
+
+def run_external_search(eng, backend, roots, sims, c_puct, evaluator, fused=False):
+    """A whole one-leaf search of `roots` through the step-wise C-ABI (run_schedule) with no fpc_search_set_leaves call."""
+    eng.search_begin(roots, c_puct)
+    run_schedule(eng, backend, [1] * sims, evaluator, fused)
     return eng.search_results(roots=roots)
+
+
+def roots_of(boards_o, R):
+    """oracle boards -> engine PODs: side to move, piece lists in their order, castling rights"""
+    from oracle import orc
+    out = []
+    for b in boards_o:
+        fb = fpc_ffi.board_from_lists(R, b.turn, orc.lists_of(b))
+        for c in range(4):
+            fb.castle[c] = b.castle[c]
+        out.append(fb)
+    return out
 
 
 def expand_promos(moves):

@@ -1,13 +1,19 @@
-"""Plain-Python model of subtree reuse (include/fpc_engine.h fpc_search_advance): the search of
-tests/leafpar_model.py on trees that PERSIST from ply to ply.  `Model.search` runs simulations on the trees as they are,
-`Model.advance` re-roots every kept game on the root child that was played: the child's object subtree is kept as it is
-(statistics, priors, children's order, every state already made), the state of a child that was never selected is made
-with orc.take_action and nothing else, an already expanded new root gets the root noise.
+"""Plain-Python model of the engine's search beyond the oracle's orc_search (oracle/fpc_oracle.cpp): up to K leaves per
+game per simulation step, kept apart by virtual loss (include/fpc_engine.h fpc_search_set_leaves), on
+trees that PERSIST from ply to ply (fpc_search_advance).  `Model.search` runs simulations on the trees
+as they are, `Model.advance` re-roots every kept game on the root child that was played: the child's object subtree is
+kept as it is (statistics, priors, children's order, every state already made), the state of a child that was never
+selected is made with orc.take_action and nothing else, an already expanded new root gets the root noise.  `search` is
+the one-ply form: fresh trees, one Model.search.
 
-Board work goes through the oracle's primitives and the priors through orc_policy_priors, as in leafpar_model.
+Board work goes through the oracle's primitives (orc.legal_moves / game_result / take_action / encode) and the priors
+through orc_policy_priors, so that the model and the kernels meet at bit level.  Selection arithmetic is fp64 without
+contraction (Python floats), the log table is math.log(math.sqrt(n)) as the host table is; f32 work (values, root
+noise) is done on numpy float32 scalars.
 
-Also here: `run_plies`, which drives an engine ply by ply through the step-wise C-ABI (fpc_search_begin once, then
-fpc_search_advance), the pick rule of the tests, and the comparison helpers.
+Also here: `run_steps` / `run_stepwise` / `run_plies`, which drive an engine through the step-wise C-ABI the way
+mcts.MCTS does with K leaves (the loop itself is fpc_testlib.run_schedule), the pick rule of the tree-reuse tests, and
+the comparison helpers.
 """
 import ctypes as C
 import math
@@ -15,17 +21,47 @@ import math
 import numpy as np
 
 import fpc_ffi
-import leafpar_model as lm
+from fpc_testlib import run_schedule
 from oracle import orc
 
-RULES_PUCT, RULES_ROTATION = lm.RULES_PUCT, lm.RULES_ROTATION
+RULES_PUCT, RULES_ROTATION = 1, 2
+
+
+class _Node:
+    __slots__ = ("N", "W", "VL", "P", "flat", "parent", "children", "state")
+
+    def __init__(self, P, flat, parent, state=None):
+        self.N, self.W, self.VL = 1, 0.0, 0      # node.h:28 default visit_count 1 (Q1)
+        self.P, self.flat, self.parent = P, flat, parent
+        self.children = []                       # parent / children hold node OBJECTS
+        self.state = state                       # made from the parent's state the first time the node is reached
+
+
+def _priors(logits_row, R, rot, legal):
+    L = orc.lib()
+    lg = np.ascontiguousarray(logits_row, dtype=np.float32)
+    lf = np.ascontiguousarray(legal, dtype=np.int32)
+    out = np.zeros(max(len(legal), 1), dtype=np.float32)
+    rc = L.orc_policy_priors(lg.ctypes.data_as(C.POINTER(C.c_float)), R, rot, lf.ctypes.data_as(C.POINTER(C.c_int)),
+                             len(legal), out.ctypes.data_as(C.POINTER(C.c_float)))
+    return rc, out[:len(legal)]
+
+
+def schedule(sims, leaves):
+    """leaves per step: an int K -> ceil(sims / K) steps of K, the last one of the remainder; a list is taken as it is"""
+    if not isinstance(leaves, int):
+        return list(leaves)
+    steps = (sims + leaves - 1) // leaves
+    return [leaves if s + 1 < steps else sims - leaves * (steps - 1) for s in range(steps)]
 
 
 class Model:
     def __init__(self, boards, R, INV, Cpuct, evaluator, rules=0, vl=1.0, noise_eps=0.0):
+        """boards: orc boards (mutated like the engine mutates its roots' piece lists).  evaluator: numpy callable
+        enc[B,24,R,R] -> (logits[B,A], value[B])."""
         self.R, self.INV, self.Cpuct, self.ev, self.rules, self.vl = R, INV, float(Cpuct), evaluator, rules, float(vl)
         self.noise, self.noise_eps = None, noise_eps
-        self.roots = [lm._Node(0.0, -1, None, state=b) for b in boards]      # parent / children hold node OBJECTS here
+        self.roots = [_Node(0.0, -1, None, state=b) for b in boards]
         self.alive = [True] * len(boards)
         self.sims_done = [0] * len(boards)
         self.counts = {"collisions": 0, "terminals": 0}
@@ -45,7 +81,7 @@ class Model:
         return [np.float32((one - eps) * np.float32(p)) + np.float32(eps * np.float32(gm[j] / sg)) for j, p in enumerate(pri)]
 
     @staticmethod
-    def _backprop(path, v):
+    def _backprop(path, v):                      # node.cpp:133-142 along the descent path: leaf +v, parent -v, ...
         v = np.float32(v)
         for nd in reversed(path):
             nd.W += float(v)
@@ -53,10 +89,11 @@ class Model:
             v = -v
 
     def search(self, sims, leaves=1):
-        """`sims` more simulations on the trees as they stand; rc as leafpar_model.search"""
+        """`sims` more simulations on the trees as they stand; leaves: K, or a list of leaves per step (schedule()).
+        rc: 0, -2 (no child selectable), -3 (policy error), -4 (move failed)"""
         orc.set_rules(self.rules)
         try:
-            return self._search(lm.schedule(sims, leaves))
+            return self._search(schedule(sims, leaves))
         finally:
             orc.set_rules(0)
 
@@ -66,6 +103,7 @@ class Model:
         for ks in sched:
             nrows = ks * G
             rows = [None] * nrows
+            # ---- selection: per game, ks descents in sequence; collision / terminal leaf end the game's step
             for g in range(G):
                 if not self.alive[g]:
                     continue
@@ -92,7 +130,7 @@ class Model:
                             return -2
                         nd = best
                         path.append(nd)
-                    if nd.VL > 0:
+                    if nd.VL > 0:                # collision: nothing is touched
                         self.counts["collisions"] += 1
                         break
                     if nd.state is None:
@@ -101,7 +139,7 @@ class Model:
                             return -4
                         nd.state = st
                     res = orc.game_result(nd.state, R, INV)
-                    if res != 0:
+                    if res != 0:                 # node.cpp:31-42, Q5
                         self._backprop(path, 0.0 if res == 3 else -1.0)
                         self.sims_done[g] += 1
                         self.alive[g] = False
@@ -114,13 +152,15 @@ class Model:
             live = [r for r in range(nrows) if rows[r] is not None]
             if not live:
                 continue
+            # ---- evaluation of rows 0 .. ks*G-1, dead rows all-zero
             states = [rows[r][1].state for r in live]
             enc = np.zeros((nrows, 24, R, R), dtype=np.float32)
-            enc[live] = orc.encode(states, R)
+            enc[live] = orc.encode(states, R)    # rotation: the first live row's turn (Q6) or each row's own
             logits, value = self.ev(enc)
             logits = np.asarray(logits, dtype=np.float32).reshape(nrows, -1)
             value = np.asarray(value, dtype=np.float32).reshape(nrows)
             turn0 = states[0].turn
+            # ---- expansion: per game, live rows in ascending k
             for g in range(G):
                 for k in range(ks):
                     row = rows[k * G + g]
@@ -129,7 +169,7 @@ class Model:
                     _, nd, path, legal = row
                     r = k * G + g
                     rot = nd.state.turn if rules & RULES_ROTATION else turn0
-                    prc, pri = lm._priors(logits[r], R, rot, legal)
+                    prc, pri = _priors(logits[r], R, rot, legal)
                     if prc:
                         return -3
                     if self.noise is not None and nd is self.roots[g]:
@@ -140,8 +180,8 @@ class Model:
                     self.sims_done[g] += 1
                     for j, fl in enumerate(legal):
                         if pri[j] == 0:
-                            continue
-                        nd.children.append(lm._Node(float(pri[j]), fl, nd))
+                            continue             # torch.nonzero drops exact zeros
+                        nd.children.append(_Node(float(pri[j]), fl, nd))
         return 0
 
     def advance(self, src_games, flats):
@@ -170,6 +210,7 @@ class Model:
         return [r.N for r in roots]
 
     def results(self):
+        """orc.search's format + "grand" per root child"""
         out = []
         for g, root in enumerate(self.roots):
             kids = root.children
@@ -182,53 +223,34 @@ class Model:
         return out
 
 
-# ---- the engine, ply by ply ---------------------------------------------------------------------------------------
-def run_steps(eng, backend, sims, evaluator, K=1, vl=1.0, fused=True):
+def search(boards, R, INV, sims, Cpuct, evaluator, leaves, vl=1.0, rules=0, noise=None, noise_eps=0.0):
+    """One ply on fresh trees.  noise: float32 [G][MAX_MOVES] gamma draws or None.
+    Returns (rc of Model.search, Model.results() or None, counts {"collisions", "terminals"})."""
+    model = Model(boards, R, INV, Cpuct, evaluator, rules=rules, vl=vl, noise_eps=noise_eps)
+    model.set_noise(noise)
+    rc = model.search(sims, leaves)
+    return rc, model.results() if rc == 0 else None, model.counts
+
+
+# ---- the engine through the step-wise C-ABI -----------------------------------------------------------------------
+def run_steps(eng, backend, sims, evaluator, K=1, vl=1.0, fused=True, begin=None):
     """`sims` simulations of the search in progress (after search_begin or search_advance) through the step-wise
-    entry points with K leaves per step -- leafpar_model.run_stepwise without its search_begin / search_results"""
-    G, R = eng.G, eng.R
-    sched = lm.schedule(sims, K)
-    steps = len(sched)
-    eng.set_leaves(sched[0] if steps else K, vl)
-    keep = []
-    n_live, enc_ptr = eng.search_select() if steps else (0, None)
-    for s in range(steps):
-        last = s == steps - 1
-        rows = sched[s] * G
-        if not last:
-            eng.set_leaves(sched[s + 1], vl)
-        if n_live == 0:
-            if not last:
-                n_live, enc_ptr = eng.search_select()
-            continue
-        if backend == "emul":
-            enc = np.ctypeslib.as_array(C.cast(enc_ptr, C.POINTER(C.c_float)), shape=(rows, 24, R, R))
-            lg, v = evaluator(enc.copy())
-            lg = np.ascontiguousarray(lg, dtype=np.float32)
-            v = np.ascontiguousarray(v, dtype=np.float32)
-            keep = [lg, v]
-            lp, vp = lg.ctypes.data, v.ctypes.data
-        else:
-            import torch
-            from fpc_testlib import DevPtr
-            enc = torch.as_tensor(DevPtr(enc_ptr, (rows, 24, R, R)), device="cuda").cpu().numpy()
-            lg, v = evaluator(enc)
-            lg_t = torch.from_numpy(np.ascontiguousarray(lg, dtype=np.float32)).cuda()
-            v_t = torch.from_numpy(np.ascontiguousarray(v, dtype=np.float32)).cuda()
-            torch.cuda.synchronize()
-            keep = [lg_t, v_t]
-            lp, vp = lg_t.data_ptr(), v_t.data_ptr()
-        if fused and not last:
-            n_live, enc_ptr = eng.search_expand_select(lp, vp)
-        else:
-            eng.search_expand(lp, vp)
-            if not last:
-                n_live, enc_ptr = eng.search_select()
-        if backend != "emul":
-            import torch
-            torch.cuda.synchronize()
-    del keep
+    entry points with K leaves per step (schedule(): an int K, or a list of leaves per step), each step's count set
+    through set_leaves before its selection.  begin: (roots, c_puct) of a search to begin first, once the first step's
+    count is set.  evaluator: numpy callable on [rows,24,R,R]."""
+    sched = schedule(sims, K)
+    K = K if isinstance(K, int) else sched[0]
+    eng.set_leaves(sched[0] if sched else K, vl)
+    if begin is not None:
+        eng.search_begin(*begin)
+    run_schedule(eng, backend, sched, evaluator, fused, set_leaves=lambda k: eng.set_leaves(k, vl))
     eng.set_leaves(K, vl)
+
+
+def run_stepwise(eng, backend, roots, sims, c_puct, evaluator, leaves, vl=1.0, fused=True):
+    """a whole search of `roots` with `leaves` leaves per step: run_steps between search_begin and search_results"""
+    run_steps(eng, backend, sims, evaluator, leaves, vl, fused, begin=(roots, c_puct))
+    return eng.search_results(roots=roots)
 
 
 def run_plies(eng, backend, roots, plan, evaluator, K=1, c_puct=3.0, vl=1.0, fused=True):
@@ -296,8 +318,10 @@ def same_state(fb, ob):
             list(fb.king) == list(ob.king) and list(fb.castle) == list(ob.castle))
 
 
-def compare(eng, res, model, tag, grand_every=5):
-    """engine results vs Model.results(), bit for bit; the second level for every `grand_every`-th game"""
+def compare(eng, res, model, tag, grand_every=1):
+    """engine result dict vs Model.results(), bit for bit; the second level (through grandchildren) for every
+    `grand_every`-th game (0: none), under every root child the model has visited -- one that was expanded has its
+    children, a terminal one has none"""
     assert len(res["root_n"]) == len(model), (tag, "games")
     for gi, o in enumerate(model):
         n = int(res["n_children"][gi])
@@ -311,7 +335,7 @@ def compare(eng, res, model, tag, grand_every=5):
         assert same_state(res["boards"][gi], o["board"]), (tag, gi, "root state")
         if grand_every and gi % grand_every == 0:
             for ci in range(n):
-                if o["grand"][ci]:
+                if o["children"][ci][1] > 1:
                     assert eng.grandchildren(gi, ci) == o["grand"][ci], (tag, gi, ci, "second level")
 
 
@@ -327,3 +351,35 @@ def same_results(a, b, ia=None, ib=None):
         for k in ("flat", "visits", "prior", "w"):
             assert np.array_equal(a[k][x, :n], b[k][y, :n]), (k, x, y)
         assert bytes(a["boards"][x]) == bytes(b["boards"][y]), (x, y)
+
+
+def positions(R, n, seed, near_end=False, rules=0):
+    """n seeded positions from random playouts through the oracle (mid-game), or `near_end`: a few plies before the
+    end of a random game, so that searches meet terminal leaves.  Returns orc boards of positions still in progress."""
+    import random
+    import positions as pos
+    INV = {8: 2, 10: 2, 13: 3, 14: 3}[R]
+    turn, entries = pos.start_entries(R)
+    rng = random.Random(seed)
+    out = []
+    orc.set_rules(rules)
+    try:
+        while len(out) < n:
+            b = orc.board_from_dict(R, turn, [list(e) for e in entries])
+            hist = [b]
+            for _ply in range(rng.randrange(0, 40) if not near_end else 800):
+                if orc.game_result(orc.clone(b), R, INV) != 0:
+                    break
+                flats = sorted(set(x[2] for x in orc.legal_moves(b, R, INV)))
+                b, rc = orc.take_action(b, R, flats[rng.randrange(len(flats))])
+                assert rc == 0
+                hist.append(b)
+            if near_end:
+                if orc.game_result(orc.clone(b), R, INV) == 0:
+                    continue                         # no end within the playout: another game
+                b = hist[max(0, len(hist) - 1 - rng.randrange(1, 4))]
+            if orc.game_result(orc.clone(b), R, INV) == 0:
+                out.append(b)
+    finally:
+        orc.set_rules(0)
+    return out

@@ -1,28 +1,18 @@
 """Leaf-parallel search (fpc_search_set_leaves) on the wavefront emulator (CPU): the product's tree kernels, driven
 through the step-wise C-ABI with K leaves per game per step, against the plain-Python model of the semantics
-(tests/leafpar_model.py), bit for bit: root N, children, visits, f32 priors, f64 value sums, sims_done, second-level
-visits and the root's piece-list order."""
+(tests/search_model.py), bit for bit: root N, children, visits, f32 priors, f64 value sums, sims_done, second-level
+visits and the root state, piece-list order included."""
 import numpy as np
 import pytest
 
 import evaluators
 import fpc_ffi
-import leafpar_model as lm
+import search_model as sm
 from engine_cases import _compare_search
-from fpc_testlib import make_engine
+from fpc_testlib import make_engine, roots_of
 from oracle import orc
 
 INV_OF = {8: 2, 14: 3}
-
-
-def _roots(boards_o, R):
-    out = []
-    for b in boards_o:
-        fb = fpc_ffi.board_from_lists(R, b.turn, orc.lists_of(b))
-        for c in range(4):
-            fb.castle[c] = b.castle[c]
-        out.append(fb)
-    return out
 
 
 def _engine_vs_model(R, boards_o, sims, K, kind="hash", rules=0, noise=False, vl=1.0, fused=True, seed=0):
@@ -32,21 +22,21 @@ def _engine_vs_model(R, boards_o, sims, K, kind="hash", rules=0, noise=False, vl
     gamma = None
     if noise:
         gamma = np.random.default_rng(seed).standard_gamma(0.3, size=(G, fpc_ffi.MAX_MOVES)).astype(np.float32)
-    rc, model, counts = lm.search([orc.clone(b) for b in boards_o], R, INV, sims, 3.0, ev, K, vl=vl, rules=rules,
+    rc, model, counts = sm.search([orc.clone(b) for b in boards_o], R, INV, sims, 3.0, ev, K, vl=vl, rules=rules,
                                   noise=gamma, noise_eps=0.25)
-    kmax = max(lm.schedule(sims, K))
+    kmax = max(sm.schedule(sims, K))
     eng = make_engine("emul", R, INV, max_games=G * kmax, max_sims=sims)
     try:
         eng.set_rules(rules)
         eng.set_root_noise(gamma, 0.25)
-        roots = _roots(boards_o, R)
+        roots = roots_of(boards_o, R)
         if rc == -3:
             with pytest.raises(RuntimeError, match="policy mass"):
-                lm.run_stepwise(eng, "emul", roots, sims, 3.0, ev, K, vl=vl, fused=fused)
+                sm.run_stepwise(eng, "emul", roots, sims, 3.0, ev, K, vl=vl, fused=fused)
             return "policy-error", counts
         assert rc == 0
-        res = lm.run_stepwise(eng, "emul", roots, sims, 3.0, ev, K, vl=vl, fused=fused)
-        lm.compare(eng, res, model, (R, K, kind, rules, sims))
+        res = sm.run_stepwise(eng, "emul", roots, sims, 3.0, ev, K, vl=vl, fused=fused)
+        sm.compare(eng, res, model, (R, K, kind, rules, sims))
         assert all(int(x) <= sims for x in res["sims_done"])
     finally:
         eng.close()
@@ -58,7 +48,7 @@ def _engine_vs_model(R, boards_o, sims, K, kind="hash", rules=0, noise=False, vl
     (14, 2, 13, "hash"), (14, 3, 11, "ramp"), (14, 4, 10, "hash"),
 ])
 def test_engine_equals_model_midgame(R, K, sims, kind):
-    boards = lm.positions(R, 6 if R == 8 else 4, seed=100 + 7 * K + R)
+    boards = sm.positions(R, 6 if R == 8 else 4, seed=100 + 7 * K + R)
     assert sims % K != 0 or K == 4          # most cases end with a partial step
     status, _ = _engine_vs_model(R, boards, sims, K, kind=kind, fused=(K != 3))
     assert status == "ok"
@@ -67,27 +57,27 @@ def test_engine_equals_model_midgame(R, K, sims, kind):
 @pytest.mark.parametrize("R,K", [(8, 2), (8, 3), (14, 2)])
 def test_engine_equals_model_near_end(R, K):
     """positions a few plies before the end of a game: terminal leaves during leaf-parallel steps"""
-    boards = lm.positions(R, 6, seed=5 + K, near_end=True)
+    boards = sm.positions(R, 6, seed=5 + K, near_end=True)
     status, counts = _engine_vs_model(R, boards, 17, K, kind="hash")
     assert status == "ok"
 
 
 @pytest.mark.parametrize("R", [8, 14])
 def test_fixed_rules_with_root_noise(R):
-    boards = lm.positions(R, 4, seed=41 + R, rules=15)
+    boards = sm.positions(R, 4, seed=41 + R, rules=15)
     status, _ = _engine_vs_model(R, boards, 14, 3, kind="hash", rules=15, noise=True, vl=0.5)
     assert status == "ok"
 
 
 def test_hashinf_both_refuse():
     """every legal logit -inf somewhere: the model and the engine both end the search with the policy error"""
-    statuses = [_engine_vs_model(8, lm.positions(8, 4, seed=seed), 12, 2, kind="hashinf")[0] for seed in range(3, 9)]
+    statuses = [_engine_vs_model(8, sm.positions(8, 4, seed=seed), 12, 2, kind="hashinf")[0] for seed in range(3, 9)]
     assert "policy-error" in statuses, statuses
 
 
 def test_collisions_and_terminals_met():
     """the cases of this file meet both kinds of dead row: a collision and a terminal leaf inside a leaf-parallel step"""
-    status, counts = _engine_vs_model(8, lm.positions(8, 6, seed=7, near_end=True), 17, 2, kind="hash")
+    status, counts = _engine_vs_model(8, sm.positions(8, 6, seed=7, near_end=True), 17, 2, kind="hash")
     assert status == "ok" and counts["collisions"] > 0 and counts["terminals"] > 0, counts
 
 
@@ -96,14 +86,14 @@ def test_collisions_and_terminals_met():
 def test_leaves_changed_during_search(sched, fused):
     """set_leaves between the steps of a running search, including 1 -> K while a one-leaf selection is pending
     (that selection holds no pending visits: it is expanded as one leaf per game, the next one is leaf-parallel)"""
-    boards = lm.positions(8, 6, seed=61)
+    boards = sm.positions(8, 6, seed=61)
     status, _ = _engine_vs_model(8, boards, sum(sched), list(sched), kind="hash", fused=fused)
     assert status == "ok"
 
 
 def test_set_leaves_one_equals_oracle():
     R, INV = 8, 2
-    boards = lm.positions(R, 5, seed=77)
+    boards = sm.positions(R, 5, seed=77)
     ev = evaluators.make("hash", R)
     rc, oref = orc.search([orc.clone(b) for b in boards], R, INV, 12, 3.0, ev)
     assert rc == 0
@@ -111,7 +101,7 @@ def test_set_leaves_one_equals_oracle():
     try:
         eng.set_leaves(2)
         eng.set_leaves(1)
-        res = lm.run_stepwise(eng, "emul", _roots(boards, R), 12, 3.0, ev, 1)
+        res = sm.run_stepwise(eng, "emul", roots_of(boards, R), 12, 3.0, ev, 1)
         _compare_search(res, oref, "leaves=1")
     finally:
         eng.close()
@@ -125,7 +115,7 @@ def test_argument_validation():
             with pytest.raises(RuntimeError):
                 eng.set_leaves(*bad)
         eng.set_leaves(fpc_ffi.MAX_LEAVES, 0.0)
-        boards = _roots(lm.positions(R, 2, seed=1), R)
+        boards = roots_of(sm.positions(R, 2, seed=1), R)
         with pytest.raises(RuntimeError, match="max_games"):      # 8 leaves x 2 games > 8 rows
             eng.search_begin(boards, 3.0)
         eng.set_leaves(4)
@@ -155,10 +145,10 @@ def test_mcts_dropin_external_evaluator():
     from mcts import MCTS
     R, INV = 8, 2
     az = dropin_cases.setup("emul", R)
-    boards = lm.positions(R, 5, seed=19)
+    boards = sm.positions(R, 5, seed=19)
     ev = evaluators.make("hash", R)
     sims = 9
-    rc, model, _ = lm.search([orc.clone(b) for b in boards], R, INV, sims, 3.0, ev, 2)
+    rc, model, _ = sm.search([orc.clone(b) for b in boards], R, INV, sims, 3.0, ev, 2)
     assert rc == 0
 
     rows = []
@@ -171,7 +161,7 @@ def test_mcts_dropin_external_evaluator():
             lg, v = ev(enc.numpy())
             return torch.from_numpy(np.ascontiguousarray(lg)), torch.from_numpy(np.ascontiguousarray(v)).view(-1, 1)
 
-    games = [FourPlayerChess._wrap(fb) for fb in _roots(boards, R)]
+    games = [FourPlayerChess._wrap(fb) for fb in roots_of(boards, R)]
     mc = MCTS(FourPlayerChess, Ev(), {"num_searches": sims, "C": 3.0, "leaves_per_step": 2})
     roots = mc.search(games)
     for g, (root, o) in enumerate(zip(roots, model)):

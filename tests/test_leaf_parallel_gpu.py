@@ -1,5 +1,5 @@
 """Leaf-parallel search (fpc_search_set_leaves) on the MI355X: the product kernels against the plain-Python model
-(tests/leafpar_model.py), the fused fpc_search_run against the step-wise C-ABI fed by fpc_nn_forward (k_towerc and
+(tests/search_model.py), the fused fpc_search_run against the step-wise C-ABI fed by fpc_nn_forward (k_towerc and
 k_towerw, both policy heads, strict and fixed rules with root noise, partial last steps), more than 256 rows, and the
 reference-default shape end to end."""
 import numpy as np
@@ -7,10 +7,9 @@ import pytest
 
 import evaluators
 import fpc_ffi
-import leafpar_model as lm
-from fpc_testlib import make_engine
+import search_model as sm
+from fpc_testlib import make_engine, roots_of
 from oracle import orc
-from test_leaf_parallel_emul import _roots
 from test_nn_gpu import INV_OF, _model, _positions
 
 pytestmark = pytest.mark.gpu
@@ -19,17 +18,13 @@ pytestmark = pytest.mark.gpu
 @pytest.mark.parametrize("R,G,sims,K,kind", [(8, 48, 100, 2, "hash"), (8, 64, 120, 3, "ramp"), (14, 48, 101, 2, "hash")])
 def test_engine_equals_model(R, G, sims, K, kind):
     INV = INV_OF[R]
-    boards = lm.positions(R, G, seed=200 + K)
+    boards = sm.positions(R, G, seed=200 + K)
     ev = evaluators.make(kind, R)
-    rc, model, counts = lm.search([orc.clone(b) for b in boards], R, INV, sims, 3.0, ev, K)
+    rc, model, counts = sm.search([orc.clone(b) for b in boards], R, INV, sims, 3.0, ev, K)
     assert rc == 0 and counts["collisions"] > 0
     eng = make_engine("gpu", R, INV, max_games=G * K, max_sims=sims)
-    res = lm.run_stepwise(eng, "gpu", _roots(boards, R), sims, 3.0, ev, K)
-    lm.compare(eng, res, model, (R, G, K, kind), grand=False)
-    for g in range(0, G, 7):
-        for ci in range(int(res["n_children"][g])):
-            if model[g]["children"][ci][1] > 1:
-                assert eng.grandchildren(g, ci) == model[g]["grand"][ci]
+    res = sm.run_stepwise(eng, "gpu", roots_of(boards, R), sims, 3.0, ev, K)
+    sm.compare(eng, res, model, (R, G, K, kind), grand_every=7)
     eng.close()
 
 
@@ -59,7 +54,7 @@ def _fused_vs_stepwise(R, G, blocks, hidden, dtype, rules, K, sims, noise=False)
         return lg.cpu().numpy(), va.cpu().numpy()
 
     roots_b = [fpc_ffi.clone_board(b) for b in boards]
-    res_b = lm.run_stepwise(eng, "gpu", roots_b, sims, 3.0, ev, K)
+    res_b = sm.run_stepwise(eng, "gpu", roots_b, sims, 3.0, ev, K)
     for k in ("root_n", "n_children", "sims_done", "flat", "visits", "prior", "w"):
         assert np.array_equal(res_a[k], res_b[k]), k
     for a, b in zip(roots_a, roots_b):

@@ -1,6 +1,6 @@
 """Subtree reuse (fpc_search_advance) on the wavefront emulator (CPU): the product's k_tree_advance and tree kernels,
 driven ply by ply through the step-wise C-ABI, against the plain-Python model with persistent trees
-(tests/treereuse_model.py), bit for bit.  The cases are those of tests/test_tree_reuse_gpu.py with fewer games."""
+(tests/search_model.py), bit for bit.  The cases are those of tests/test_tree_reuse_gpu.py with fewer games."""
 import pytest
 
 import treereuse_cases as tc

@@ -1,5 +1,5 @@
 """Subtree reuse (fpc_search_advance) on the MI355X: k_tree_advance and the tree kernels against the plain-Python model
-with persistent trees (tests/treereuse_model.py) at the full case sizes, the structural, dropping, budget and error
+with persistent trees (tests/search_model.py) at the full case sizes, the structural, dropping, budget and error
 checks of tests/treereuse_cases.py, the fused fpc_search_run after every advance against the step-wise C-ABI fed by
 fpc_nn_forward (k_towerc and k_towerw), the legal-only head through the plies, and the self-play loop.  Everything is
 compared exactly."""
@@ -7,8 +7,8 @@ import numpy as np
 import pytest
 
 import fpc_ffi
+import search_model as sm
 import treereuse_cases as tc
-import treereuse_model as tm
 from fpc_testlib import make_engine
 from test_nn_gpu import INV_OF, _model, _positions
 
@@ -82,17 +82,17 @@ def test_fused_equals_stepwise(R, hidden, kernel):
         n, stats, expanded = sims, {"visited": 0, "unvisited": 0}, 0
         for ply in range(plies):
             fused.search_run(n)
-            tm.run_steps(step, "gpu", n, ev)
+            sm.run_steps(step, "gpu", n, ev)
             a, b = fused.search_results(), step.search_results()
-            tm.same_results(a, b)
+            sm.same_results(a, b)
             assert int(a["sims_done"].sum()) > len(a["root_n"]) * n // 2
             if ply + 1 == plies:
                 break
-            src, flats = tm.pick_rule(a, stats)
+            src, flats = sm.pick_rule(a, stats)
             ka, kb = fused.search_advance(flats, src), step.search_advance(flats, src)
             assert np.array_equal(ka, kb)
             after = fused.search_results()
-            tm.same_results(after, step.search_results())
+            sm.same_results(after, step.search_results())
             expanded += int((after["n_children"] > 0).sum())
             n = _room(fused, ka, sims)
         assert stats["visited"] > 0 and stats["unvisited"] > 0 and expanded > 0, (stats, expanded)
@@ -115,7 +115,7 @@ def test_legal_head_through_the_plies():
             eng.search_begin(_positions(R, G), 3.0)
             eng.search_run(sims)
             res, runs = eng.search_results(), []
-            src, flats = tm.pick_rule(res)
+            src, flats = sm.pick_rule(res)
             assert src == list(range(G))
             for _ply in range(1, plies):
                 if only is not None:
@@ -133,7 +133,7 @@ def test_legal_head_through_the_plies():
         finally:
             eng.close()
     for a, b in zip(*out):
-        tm.same_results(a, b, sub, None)
+        sm.same_results(a, b, sub, None)
 
 
 def test_alphazero_reuse_tree():

@@ -5,11 +5,9 @@ import pytest
 
 import evaluators
 import fpc_ffi
-import leafpar_model as lm
-import treereuse_model as tm
-from fpc_testlib import make_engine
+import search_model as sm
+from fpc_testlib import make_engine, roots_of
 from oracle import orc
-from test_leaf_parallel_emul import _roots
 
 INV_OF = {8: 2, 14: 3}
 
@@ -25,9 +23,9 @@ def engine_vs_model(backend, case, G=None, drop_first=False):
     R, G0, plies, sims, K, kind, rules, noise = CASES[case]
     G = G or G0
     INV = INV_OF[R]
-    boards = lm.positions(R, G, seed=300 + case, rules=rules)
+    boards = sm.positions(R, G, seed=300 + case, rules=rules)
     ev = evaluators.make(kind, R)
-    model = tm.Model([orc.clone(b) for b in boards], R, INV, 3.0, ev, rules=rules, noise_eps=0.25)
+    model = sm.Model([orc.clone(b) for b in boards], R, INV, 3.0, ev, rules=rules, noise_eps=0.25)
     eng = make_engine(backend, R, INV, max_games=G * K, max_sims=2 * sims)
     rng = np.random.default_rng(case)
     stats = {"visited": 0, "unvisited": 0, "expanded_roots": 0, "dropped": drop_first, "sims": []}
@@ -39,7 +37,7 @@ def engine_vs_model(backend, case, G=None, drop_first=False):
             model.set_noise(gamma)
 
     def pick(res):
-        src, flats = tm.pick_rule(res, stats)
+        src, flats = sm.pick_rule(res, stats)
         if stats["dropped"]:
             src, flats, stats["dropped"] = src[1:], flats[1:], False
         set_noise(len(flats))
@@ -48,16 +46,16 @@ def engine_vs_model(backend, case, G=None, drop_first=False):
     try:
         eng.set_rules(rules)
         set_noise(G)
-        for ply, info in enumerate(tm.run_plies(eng, backend, _roots(boards, R), [(sims, pick)] * plies, ev, K)):
+        for ply, info in enumerate(sm.run_plies(eng, backend, roots_of(boards, R), [(sims, pick)] * plies, ev, K)):
             if ply > 0:
                 kept = model.advance(info["src"], info["flats"])
                 assert [int(x) for x in info["kept"]] == kept, (case, ply, "kept visits")
-                tm.compare(eng, info["after"], model.results(), (case, ply, "after the advance"), grand_every=0)
+                sm.compare(eng, info["after"], model.results(), (case, ply, "after the advance"), grand_every=0)
                 for g, root in enumerate(model.roots):
-                    assert tm.same_state(fpc_ffi.board_of(info["roots"][g]), root.state), (case, ply, g, "roots_out")
+                    assert sm.same_state(fpc_ffi.board_of(info["roots"][g]), root.state), (case, ply, g, "roots_out")
                 stats["expanded_roots"] += int((info["after"]["n_children"] > 0).sum())
             assert model.search(info["sims"], K) == 0
-            tm.compare(eng, info["res"], model.results(), (case, ply))
+            sm.compare(eng, info["res"], model.results(), (case, ply), grand_every=5)
             stats["sims"].append(info["sims"])
     finally:
         eng.close()
@@ -69,13 +67,13 @@ def engine_vs_model(backend, case, G=None, drop_first=False):
 
 def _first_ply(backend, R, G, sims, rules=0, seed=11, K=1, max_sims=None):
     INV = INV_OF[R]
-    boards = lm.positions(R, G, seed=seed, rules=rules)
+    boards = sm.positions(R, G, seed=seed, rules=rules)
     ev = evaluators.make("hash", R)
     eng = make_engine(backend, R, INV, max_games=G * K, max_sims=max_sims or 2 * sims)
     eng.set_rules(rules)
     eng.set_leaves(K)
-    eng.search_begin(_roots(boards, R), 3.0)
-    tm.run_steps(eng, backend, sims, ev, K)
+    eng.search_begin(roots_of(boards, R), 3.0)
+    sm.run_steps(eng, backend, sims, ev, K)
     return eng, ev, eng.search_results()
 
 
@@ -85,7 +83,7 @@ def structure(backend):
     eng, _, res0 = _first_ply(backend, R, G, sims)
     try:
         stats = {"visited": 0, "unvisited": 0}
-        src, flats = tm.pick_rule(res0, stats)
+        src, flats = sm.pick_rule(res0, stats)
         assert stats["visited"] > 0 and stats["unvisited"] > 0
         kidx = [int(np.nonzero(res0["flat"][g, :res0["n_children"][g]] == f)[0][0]) for g, f in zip(src, flats)]
         grand = [eng.grandchildren(g, k) for g, k in zip(src, kidx)]
@@ -118,7 +116,7 @@ def dropping(backend):
     def run(only):
         eng, ev, res = _first_ply(backend, R, G, sims, rules=rules, seed=23)
         try:
-            src, flats = tm.pick_rule(res)
+            src, flats = sm.pick_rule(res)
             assert src == list(range(G))
             out = []
             for ply in range(2):
@@ -127,7 +125,7 @@ def dropping(backend):
                 kept = eng.search_advance(flats, src)
                 if len(used) == ply:
                     used.append(min(sims, eng.max_sims - (int(kept.max()) - 1)))
-                tm.run_steps(eng, backend, used[ply], ev)
+                sm.run_steps(eng, backend, used[ply], ev)
                 res = eng.search_results()
                 out.append(res)
                 n = len(res["root_n"])
@@ -140,7 +138,7 @@ def dropping(backend):
 
     everyone, survivors = run(None), run(sub)
     for a, b in zip(everyone, survivors):
-        tm.same_results(a, b, sub, None)
+        sm.same_results(a, b, sub, None)
         assert int(b["sims_done"].sum()) > 0
 
 
@@ -152,7 +150,7 @@ def budget(backend):
         flats = [int(res["flat"][g, int(np.argmax(res["visits"][g, :res["n_children"][g]]))]) for g in range(G)]
         kept = eng.search_advance(flats)
         assert int(kept.max()) > 1
-        tm.run_steps(eng, backend, 2 * sims - (int(kept.max()) - 1), ev)
+        sm.run_steps(eng, backend, 2 * sims - (int(kept.max()) - 1), ev)
         with pytest.raises(RuntimeError, match="max_sims"):
             eng.search_select()
         res = eng.search_results()
@@ -189,20 +187,20 @@ def errors(backend):
         wrong[2] = next(f for f in range(eng.A) if f not in taken)
         with pytest.raises(RuntimeError, match="game 2: piece missing for move"):
             eng.search_advance(wrong)
-        rc, got = tm.results_raw(eng)
+        rc, got = sm.results_raw(eng)
         assert rc == -7
         ref.search_advance(flats)
         want = ref.search_results()
         others = [0, 1, 3, 4]
-        tm.same_results(got, want, others, others)
+        sm.same_results(got, want, others, others)
         assert int(got["n_children"][2]) == 0 and int(got["root_n"][2]) == 1
-        tm.run_steps(eng, backend, sims, ev)                     # the killed game stays out of the search
-        tm.run_steps(ref, backend, sims, ev)
-        rc, got = tm.results_raw(eng)
+        sm.run_steps(eng, backend, sims, ev)                     # the killed game stays out of the search
+        sm.run_steps(ref, backend, sims, ev)
+        rc, got = sm.results_raw(eng)
         assert rc == -7 and int(got["sims_done"][2]) == 0
-        tm.same_results(got, ref.search_results(), [0, 1], [0, 1])      # strict rules: rows before the dead one see the same batch rotation
+        sm.same_results(got, ref.search_results(), [0, 1], [0, 1])      # strict rules: rows before the dead one see the same batch rotation
         # call sequence: only a search whose results have been read can be advanced
-        eng.search_begin(_roots(lm.positions(R, 2, seed=3), R), 3.0)
+        eng.search_begin(roots_of(sm.positions(R, 2, seed=3), R), 3.0)
         with pytest.raises(RuntimeError, match="fpc_search_results has not been read"):
             eng.search_advance([0, 0])
         fresh = make_engine(backend, R, INV, max_games=2, max_sims=4)
@@ -217,12 +215,12 @@ def errors(backend):
 def _episode_fns(eng, backend, ev, sims):
     def search_fn(pods):
         eng.search_begin(pods, 3.0)
-        tm.run_steps(eng, backend, sims, ev)
+        sm.run_steps(eng, backend, sims, ev)
         return eng.search_results(roots=pods)
 
     def continue_fn(keep_idx, picks, pods):
         kept = eng.search_advance(picks, keep_idx, roots=pods)
-        tm.run_steps(eng, backend, min(sims, eng.max_sims - (int(kept.max()) - 1)), ev)
+        sm.run_steps(eng, backend, min(sims, eng.max_sims - (int(kept.max()) - 1)), ev)
         return eng.search_results(roots=pods)
 
     return search_fn, continue_fn
@@ -241,7 +239,7 @@ def selfplay_loop(backend):
     episodes of an engine that has advanced before are those of an engine that never did"""
     import selfplay
     R, INV, G, sims, L = 8, 2, 6, 16, 5
-    boards = lm.positions(R, G, seed=71)
+    boards = sm.positions(R, G, seed=71)
     ev = evaluators.make("hash", R)
     args = {"temperature": 1.0, "max_game_length": L, "heuristic_weight": 0.5}
     uniforms = np.random.default_rng(5).random((L, G)).tolist()
@@ -249,9 +247,9 @@ def selfplay_loop(backend):
     fresh = make_engine(backend, R, INV, max_games=G, max_sims=2 * sims)
     try:
         search_fn, continue_fn = _episode_fns(eng, backend, ev, sims)
-        eps = selfplay.play(search_fn, eng, _roots(boards, R), args, uniforms, continue_fn=continue_fn)
+        eps = selfplay.play(search_fn, eng, roots_of(boards, R), args, uniforms, continue_fn=continue_fn)
         # ---- the model's episode
-        model = tm.Model([orc.clone(b) for b in boards], R, INV, 3.0, ev)
+        model = sm.Model([orc.clone(b) for b in boards], R, INV, 3.0, ev)
         ids = list(range(G))
         moves, pis, zs, turns = {g: [] for g in ids}, {g: [] for g in ids}, {}, {g: [] for g in ids}
         keep_pos, keep_picks, last = [], [], {}
@@ -293,8 +291,8 @@ def selfplay_loop(backend):
                 assert np.array_equal(f, mf) and np.array_equal(v, mv), e.gid
         assert max(len(e.moves) for e in eps) == L
         # ---- continue_fn=None: today's loop, also on an engine that has advanced before
-        a = selfplay.play(search_fn, eng, _roots(boards, R), args, uniforms)
-        b = selfplay.play(_episode_fns(fresh, backend, ev, sims)[0], fresh, _roots(boards, R), args, uniforms)
+        a = selfplay.play(search_fn, eng, roots_of(boards, R), args, uniforms)
+        b = selfplay.play(_episode_fns(fresh, backend, ev, sims)[0], fresh, roots_of(boards, R), args, uniforms)
         _same_episodes(a, b)
         assert any(x.moves != y.moves or [list(v) for _, _, v in x.entries] != [list(v) for _, _, v in y.entries]
                    for x, y in zip(a, eps))                   # and reuse does change the searches
