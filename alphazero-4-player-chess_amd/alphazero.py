@@ -9,7 +9,14 @@ PyTorch(-ROCm):  loss = cross_entropy(policy_logits, pi) + mse(value, z)   (alph
 `args` takes the reference's keys (alphazero.py:291-306): max_game_length, C, num_searches,
 num_iterations, num_games, num_parallel_games, batch_size, temperature, heuristic_weight,
 replay_buffer_capacity, validation_buffer_capacity.  Beyond the reference: reuse_tree (default False) -- self-play keeps
-the played move's subtree from ply to ply (play(); arena.py and the drop-in MCTS.search(games) never do).
+the played move's subtree from ply to ply (play(); arena.py and the drop-in MCTS.search(games) never do);
+device_replay (default False) -- both replay buffers live in device memory as fpc_tuple records
+(replay_buffer.DeviceReplayBuffer): play() collects each ply's tuples on the device and pushes them into the rings
+device to device, and every training batch is decoded by one kernel launch instead of one engine call per sample.
+Same contents, entry for entry, and the same batches, bit for bit, as the host buffers give.  The rings belong to the
+process-wide engine handle, which is therefore sized when this object is made and must not be re-created afterwards,
+and which has one pair of rings: a second AlphaZero with device_replay in the same process takes them over (it empties
+them), and the first one's next use of its buffers raises.
 """
 import numpy as np
 import torch
@@ -19,7 +26,7 @@ import alphazero_cpp as az
 import selfplay
 import tuples
 from mcts import MCTS
-from replay_buffer import ReplayBuffer
+from replay_buffer import DeviceReplayBuffer, ReplayBuffer
 
 
 class AlphaZero:
@@ -28,8 +35,15 @@ class AlphaZero:
         self.game_init_args = game_init_args
         self.scheduler = torch.optim.lr_scheduler.StepLR(optimizer, step_size=1000, gamma=0.1)   # alphazero.py:25-27
         self.mcts = MCTS(gameType, evaluator if evaluator is not None else model, args)
-        self.experience_buffer = ReplayBuffer(args["replay_buffer_capacity"])
-        self.validation_buffer = ReplayBuffer(args["validation_buffer_capacity"])
+        self.device_replay = bool(args.get("device_replay", False)) if hasattr(args, "get") else False
+        if self.device_replay:
+            eng = self._engine()
+            dev = None if eng.host_memory else "cuda"                 # None: the test-suite's emulator build writes host memory
+            self.experience_buffer = DeviceReplayBuffer(eng, 0, args["replay_buffer_capacity"], device=dev)
+            self.validation_buffer = DeviceReplayBuffer(eng, 1, args["validation_buffer_capacity"], device=dev)
+        else:
+            self.experience_buffer = ReplayBuffer(args["replay_buffer_capacity"])
+            self.validation_buffer = ReplayBuffer(args["validation_buffer_capacity"])
         self.gen = torch.Generator().manual_seed(seed) if seed is not None else None
         self.history = []
 
@@ -37,15 +51,20 @@ class AlphaZero:
     def _new_game(self):
         return self.gameType() if not self.game_init_args else self.gameType(*self.game_init_args)
 
-    def play(self):
+    def _engine(self):
         G = int(self.args["num_parallel_games"])
-        games = [self._new_game() for _ in range(G)]
         # same (rows = games x leaves_per_step, sims, dtype) request as MCTS.search makes, so the handle is not re-created under us
         # args["reuse_tree"] (opt-in, default off; not reference semantics): every ply after the first continues on the
         # subtree of the move played (MCTS.continue_search) -- with the internal network or an external evaluator alike.
         # The handle then holds 2 * num_searches simulations: the visits kept from the last ply count against max_sims
         reuse = bool(self.args.get("reuse_tree", False)) if hasattr(self.args, "get") else False
-        eng = az.engine(self.mcts.engine_rows(G), int(self.args["num_searches"]) * (2 if reuse else 1), self.mcts.nn_dtype if self.mcts._native else None)
+        return az.engine(self.mcts.engine_rows(G), int(self.args["num_searches"]) * (2 if reuse else 1), self.mcts.nn_dtype if self.mcts._native else None)
+
+    def play(self):
+        G = int(self.args["num_parallel_games"])
+        games = [self._new_game() for _ in range(G)]
+        reuse = bool(self.args.get("reuse_tree", False)) if hasattr(self.args, "get") else False
+        eng = self._engine()
         L = int(self.args["max_game_length"])
         uniforms = torch.rand(L, G, generator=self.gen, dtype=torch.float64).tolist()
 
@@ -64,8 +83,32 @@ class AlphaZero:
         def continue_fn(keep_idx, picks, pods):
             return self.mcts.continue_search(pods, keep_idx, picks)
 
-        episodes = selfplay.play(search_fn, eng, [g._b for g in games], self.args, uniforms, continue_fn=continue_fn if reuse else None)
+        where = {}                                        # device replay: (game id, ply) -> index of the collected tuple
+
+        def on_searched(ids, ply):
+            for g in ids:
+                where[(g, ply)] = len(where)
+            eng.collect_tuples(ids, ply)
+
+        if self.device_replay:
+            if eng is not self.experience_buffer.eng:
+                raise RuntimeError("device_replay: the engine handle was re-created (alphazero_cpp.engine grew or was "
+                                   "reconfigured) and the replay rings went with it")
+            eng.tuples_reserve(L * G)
+        episodes = selfplay.play(search_fn, eng, [g._b for g in games], self.args, uniforms, continue_fn=continue_fn if reuse else None,
+                                 on_searched=on_searched if self.device_replay else None)
         split = self.args["replay_buffer_capacity"] / (self.args["replay_buffer_capacity"] + self.args["validation_buffer_capacity"])
+        if self.device_replay:
+            z_team = np.zeros((2, len(episodes)), np.float32)      # z by (game, team of the side to move), as the Episodes have it
+            src, ring_of = [], []
+            for k, ep in enumerate(episodes):
+                for ply, ((pod, _, _), z) in enumerate(zip(ep.entries, ep.z)):
+                    z_team[pod.turn & 1, k] = z
+                    src.append(where[(ep.gid, ply)])
+                    ring_of.append(0 if torch.rand(1, generator=self.gen).item() < split else 1)
+            eng.tuples_set_z([ep.gid for ep in episodes], z_team[0], z_team[1])
+            eng.replay_push(src_index=src, ring_of=ring_of)
+            return episodes
         for ep in episodes:                               # handle_terminal_state, alphazero.py:53-78
             for (pod, flats, visits), z in zip(ep.entries, ep.z):
                 buf = self.experience_buffer if torch.rand(1, generator=self.gen).item() < split else self.validation_buffer
@@ -74,6 +117,9 @@ class AlphaZero:
 
     # ---- optimiser step (alphazero.py:181-258) ----
     def _batch(self, sample):
+        if self.device_replay:                            # DeviceReplayBuffer.sample: the decoded batch itself
+            dev = next(self.model.parameters()).device
+            return tuple(t.to(dev) for t in sample)
         eng = az.engine()
         A = self.gameType.action_space_size
         dev = next(self.model.parameters()).device

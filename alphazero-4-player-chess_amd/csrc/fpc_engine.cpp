@@ -89,6 +89,15 @@ struct fpc_engine {
   int gather_stride = 0;
   size_t gather_cap = 0;            // tuples the receive buffer holds (world x padded count)
   std::vector<int> gather_counts;
+  // ---- device-resident replay (fpc_replay_*): the cursors live here, the records on the device
+  struct Ring {
+    fpc_tuple *d = nullptr;
+    int cap = 0, size = 0, next = 0;   // ReplayBuffer's capacity, len(_items), _next
+  } ring[FPC_REPLAY_RINGS + 1];     // + FPC_REPLAY_SCRATCH
+  int *d_rp_idx = nullptr;          // index staging of one push ([2][rp_idx_cap / 2] source | destination) or one batch (slots)
+  size_t rp_idx_cap = 0;
+  hipEvent_t rp_ev[2] = {nullptr, nullptr};   // around k_replay_decode while fpc_set_timing is on
+  float rp_decode_ms = -1.f;
   // ---- stats
   bool timing = false;
   int policy_mode = 0;            // FPC_POLICY_FULL / FPC_POLICY_LEGAL (fpc_search_run only)
@@ -385,6 +394,7 @@ void fpc_destroy(fpc_engine *e) {
 #endif
   for (void *p : e->allocs) (void)hipFree(p);
   for (auto &ev : e->evpool) if (ev) (void)hipEventDestroy(ev);
+  for (auto &ev : e->rp_ev) if (ev) (void)hipEventDestroy(ev);
   if (e->stream) (void)hipStreamDestroy(e->stream);
   delete e;
 }
@@ -939,6 +949,173 @@ int fpc_tuples_read(fpc_engine *e, fpc_tuple *host_out, int first, int n) {
 }
 
 // ------------------------------------------------------------------------------------------------
+// device-resident replay
+namespace {
+void dfree(fpc_engine *e, void *p) {
+  if (!p) return;
+  (void)hipFree(p);
+  e->allocs.erase(std::find(e->allocs.begin(), e->allocs.end(), p));
+}
+
+int ensure_replay_idx(fpc_engine *e, size_t ints) {
+  if (ints <= e->rp_idx_cap) return 0;
+  dfree(e, e->d_rp_idx);
+  e->d_rp_idx = nullptr;
+  e->rp_idx_cap = 0;
+  const size_t cap = std::max<size_t>(ints, 1024);
+  int r;
+  if ((r = dalloc(e, &e->d_rp_idx, cap))) return r;
+  e->rp_idx_cap = cap;
+  return 0;
+}
+
+bool bad_ring(int ring) { return ring < 0 || ring > FPC_REPLAY_SCRATCH; }
+}  // namespace
+
+int fpc_replay_reserve(fpc_engine *e, int ring, int capacity) {
+  if (!e || bad_ring(ring) || capacity < 1) return fail(e, FPC_EINVAL, "fpc_replay_reserve: ring %d / capacity %d out of range", ring, capacity);
+  USE_DEV(e);
+  fpc_engine::Ring &g = e->ring[ring];
+  // k_replay_store addresses both rings through one int index space
+  if (ring < FPC_REPLAY_RINGS && (long long)capacity + e->ring[1 - ring].cap > 0x7fffffffLL) return fail(e, FPC_EINVAL, "fpc_replay_reserve: the two capacities together exceed 2^31 - 1");
+  if (capacity != g.cap) {       // the new ring exists before the old one goes: FPC_ENOMEM leaves the ring as it was
+    fpc_tuple *d = nullptr;
+    int r;
+    if ((r = dalloc(e, &d, (size_t)capacity))) return r;
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    dfree(e, g.d);
+    g.d = d;
+    g.cap = capacity;
+  }
+  g.size = g.next = 0;           // same capacity: the allocation stays, only the cursors go back
+  return 0;
+}
+
+int fpc_replay_size(fpc_engine *e, int ring) {
+  if (!e || bad_ring(ring)) return fail(e, FPC_EINVAL, "fpc_replay_size: ring %d out of range", ring);
+  return e->ring[ring].size;
+}
+
+int fpc_replay_push(fpc_engine *e, int source, const int *src_index, const int8_t *ring_of, int m) {
+  if (!e || m < 0 || (source != FPC_REPLAY_COLLECTED && source != FPC_REPLAY_GATHERED)) return fail(e, FPC_EINVAL, "fpc_replay_push: bad argument");
+  const fpc_tuple *src = nullptr;
+  int count = 0;
+  if (source == FPC_REPLAY_COLLECTED) {
+    src = e->d_tuples;
+    count = e->tuple_count;
+  } else {
+    if (!e->d_gather || e->gather_counts.empty()) return fail(e, FPC_ESTATE, "fpc_replay_push: fpc_allgather_tuples has not been called");
+    src = e->d_gather;
+    for (int c : e->gather_counts) count += c;
+  }
+  // every argument is checked before a cursor moves
+  for (int j = 0; j < m; ++j) {
+    const int rg = ring_of ? (int)ring_of[j] : 0, si = src_index ? src_index[j] : j;
+    if (rg < -1 || rg >= FPC_REPLAY_RINGS) return fail(e, FPC_EINVAL, "fpc_replay_push: ring_of[%d] = %d outside -1..%d", j, rg, FPC_REPLAY_RINGS - 1);
+    if (si < 0 || si >= count) return fail(e, FPC_EINVAL, "fpc_replay_push: source index %d (entry %d) outside 0..%d", si, j, count - 1);
+    if (rg >= 0 && !e->ring[rg].d) return fail(e, FPC_ESTATE, "fpc_replay_push: ring %d has not been reserved (fpc_replay_reserve)", rg);
+  }
+  USE_DEV(e);
+  fpc_engine::Ring cur[FPC_REPLAY_RINGS];
+  for (int k = 0; k < FPC_REPLAY_RINGS; ++k) cur[k] = e->ring[k];
+  const int cap0 = cur[0].cap;
+  std::unordered_map<int, int> at;          // destination -> its entry of the launch lists (the last writer of a slot wins)
+  std::vector<int> lists[2];                // source | destination
+  for (int j = 0; j < m; ++j) {
+    const int rg = ring_of ? (int)ring_of[j] : 0;
+    if (rg < 0) continue;
+    int si = src_index ? src_index[j] : j;
+    if (source == FPC_REPLAY_GATHERED) {    // logical index -> (rank, local index): ranks are stored max-padded
+      int r = 0;
+      while (si >= e->gather_counts[r]) si -= e->gather_counts[r++];
+      si += r * e->gather_stride;
+    }
+    fpc_engine::Ring &g = cur[rg];
+    const int dst = (rg ? cap0 : 0) + g.next;       // ReplayBuffer.add: while filling up, _next == len(_items)
+    g.next = (g.next + 1) % g.cap;
+    g.size = std::min(g.size + 1, g.cap);
+    auto it = at.find(dst);
+    if (it != at.end()) lists[0][(size_t)it->second] = si;
+    else { at.emplace(dst, (int)lists[0].size()); lists[0].push_back(si); lists[1].push_back(dst); }
+  }
+  const size_t k = lists[0].size();
+  if (k) {
+    int r;
+    if ((r = ensure_replay_idx(e, 2 * k))) return r;
+    HIPCHK(e, hipMemcpyAsync(e->d_rp_idx, lists[0].data(), k * sizeof(int), hipMemcpyHostToDevice, e->stream));
+    HIPCHK(e, hipMemcpyAsync(e->d_rp_idx + k, lists[1].data(), k * sizeof(int), hipMemcpyHostToDevice, e->stream));
+    FPC_LAUNCH(k_replay_store, (int)k, 64, e->stream, src, (const int *)e->d_rp_idx, cur[0].d, cur[1].d, cap0, (const int *)(e->d_rp_idx + k), (int)k);
+    HIPCHK(e, hipGetLastError());
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+  }
+  for (int i = 0; i < FPC_REPLAY_RINGS; ++i) e->ring[i] = cur[i];
+  return 0;
+}
+
+int fpc_replay_load(fpc_engine *e, int ring, const fpc_tuple *host, int n) {
+  if (!e || bad_ring(ring) || n < 0 || (!host && n > 0)) return fail(e, FPC_EINVAL, "fpc_replay_load: bad argument");
+  fpc_engine::Ring &g = e->ring[ring];
+  if (!g.d) return fail(e, FPC_ESTATE, "fpc_replay_load: ring %d has not been reserved (fpc_replay_reserve)", ring);
+  if (n == 0) return 0;
+  USE_DEV(e);
+  // record j goes to slot (next + j) mod capacity; of more than `capacity` records only the last `capacity` survive
+  const int first = std::max(0, n - g.cap);
+  int j = first;
+  while (j < n) {
+    const int slot = (int)(((long long)g.next + j) % g.cap), take = std::min(n - j, g.cap - slot);
+    HIPCHK(e, hipMemcpyAsync(g.d + slot, host + j, (size_t)take * sizeof(fpc_tuple), hipMemcpyHostToDevice, e->stream));
+    j += take;
+  }
+  HIPCHK(e, hipStreamSynchronize(e->stream));
+  g.next = (int)(((long long)g.next + n) % g.cap);
+  g.size = (int)std::min<long long>((long long)g.size + n, g.cap);
+  return 0;
+}
+
+int fpc_replay_read(fpc_engine *e, int ring, fpc_tuple *host_out, int first_slot, int n) {
+  if (!e || bad_ring(ring) || !host_out || first_slot < 0 || n < 0 || (long long)first_slot + n > e->ring[ring].size)
+    return fail(e, FPC_EINVAL, "fpc_replay_read: bad ring or slot range");
+  if (n == 0) return 0;
+  USE_DEV(e);
+  HIPCHK(e, hipMemcpyAsync(host_out, e->ring[ring].d + first_slot, (size_t)n * sizeof(fpc_tuple), hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(e, hipStreamSynchronize(e->stream));
+  return 0;
+}
+
+int fpc_replay_batch(fpc_engine *e, int ring, const int *slot, int n, float *enc_dev, float *pi_dev, float *z_dev) {
+  if (!e || bad_ring(ring) || n < 0 || !slot || !enc_dev || !pi_dev || !z_dev) return fail(e, FPC_EINVAL, "fpc_replay_batch: bad argument");
+  if (((uintptr_t)enc_dev | (uintptr_t)pi_dev) & 15) return fail(e, FPC_EINVAL, "fpc_replay_batch: enc_dev and pi_dev must be 16-byte aligned");
+  const fpc_engine::Ring &g = e->ring[ring];
+  if (!g.d) return fail(e, FPC_ESTATE, "fpc_replay_batch: ring %d has not been reserved (fpc_replay_reserve)", ring);
+  for (int i = 0; i < n; ++i)
+    if (slot[i] < 0 || slot[i] >= g.size) return fail(e, FPC_EINVAL, "fpc_replay_batch: slot[%d] = %d outside 0..%d", i, slot[i], g.size - 1);
+  if (n == 0) return 0;
+  USE_DEV(e);
+  int r;
+  if ((r = ensure_replay_idx(e, (size_t)n))) return r;
+  HIPCHK(e, hipMemcpyAsync(e->d_rp_idx, slot, (size_t)n * sizeof(int), hipMemcpyHostToDevice, e->stream));
+  if (e->timing && !e->rp_ev[0]) {
+    HIPCHK(e, hipEventCreate(&e->rp_ev[0]));
+    HIPCHK(e, hipEventCreate(&e->rp_ev[1]));
+  }
+  if (e->timing) HIPCHK(e, hipEventRecord(e->rp_ev[0], e->stream));
+  FPC_LAUNCH(k_replay_decode, n, RD_THREADS, e->stream, e->dc, (const fpc_tuple *)g.d, (const int *)e->d_rp_idx, n, enc_dev, pi_dev, z_dev);
+  HIPCHK(e, hipGetLastError());
+  if (e->timing) HIPCHK(e, hipEventRecord(e->rp_ev[1], e->stream));
+  HIPCHK(e, hipStreamSynchronize(e->stream));
+  e->rp_decode_ms = -1.f;
+  if (e->timing) HIPCHK(e, hipEventElapsedTime(&e->rp_decode_ms, e->rp_ev[0], e->rp_ev[1]));
+  return 0;
+}
+
+int fpc_replay_decode_ms(fpc_engine *e, float *ms_out) {
+  if (!e || !ms_out) return fail(e, FPC_EINVAL, "bad argument");
+  if (e->rp_decode_ms < 0.f) return fail(e, FPC_ESTATE, "fpc_replay_decode_ms: no fpc_replay_batch has run with fpc_set_timing on");
+  *ms_out = e->rp_decode_ms;
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
 // RCCL (backend "nccl" on ROCm), bound at run time: the copy PyTorch-ROCm already mapped into the
 // process is preferred (one HIP runtime, one RCCL), else the system librccl.so.
 #ifndef FPC_EMUL
@@ -1267,6 +1444,14 @@ const char *fpc_nn_kernel(fpc_engine *e) {
 #endif
 }
 void *fpc_stream(fpc_engine *e) { return e ? (void *)e->stream : nullptr; }
+
+int fpc_memory_is_host(void) {
+#ifdef FPC_EMUL
+  return 1;
+#else
+  return 0;
+#endif
+}
 
 #ifdef FPC_TREE_STAMPS
 // diagnostic builds only (tools/tree_stamps.py): the s_memtime stamps the tree kernels left for game FPC_TREE_STAMPS

@@ -14,6 +14,8 @@
 //   k_select_multi / k_expand(_legal)(_select)_multi  the same for the opt-in leaf-parallel search (K leaves per game
 //                    per step, virtual loss; fpc_search_set_leaves): the descent is select_game's, row k*G + g per leaf
 //   k_tree_advance   opt-in subtree reuse (fpc_search_advance): re-roots every game's tree on the move played, out of place
+//   k_replay_store / k_replay_decode  opt-in device-resident replay (fpc_replay_*): training records into ring slots, and any
+//                    selection of slots into the trainer's dense (state, pi, z) batch in one launch  (alphazero.py:71-73, :104-110)
 //
 // Reference semantics (file:line relative to /root/reference/src/cpp) are restated per function.
 // Nothing here is translated from the reference: its board is a pointer-rich mailbox + std::vector
@@ -1228,6 +1230,92 @@ __global__ void __launch_bounds__(256) k_tuples_set_z(fpc_tuple *recs, int count
   const int game = recs[i].game;
   for (int k = 0; k < n; ++k)
     if (game_id[k] == game) { recs[i].z = (recs[i].turn & 1) ? z1[k] : z0[k]; return; }
+}
+
+// ================================================================================================
+// device-resident replay (fpc_replay_*): the rings hold fpc_tuple records; a minibatch is decoded in one launch
+// ================================================================================================
+struct alignas(16) Vec16 { uint32_t w[4]; };      // one 16-byte access per lane (global_load/store_dwordx4)
+static_assert(sizeof(fpc_tuple) == 80 * sizeof(Vec16), "k_replay_store copies a record as 64 + 16 16-byte pieces");
+
+// m whole records src[src_idx[j]] -> ring slot dst_idx[j], one wave per record.  Destination index space: ring 0's slots,
+// then ring 1's (d >= cap0: slot d - cap0 of ring 1).  The host guarantees that no two entries name the same destination.
+__global__ void __launch_bounds__(64) k_replay_store(const fpc_tuple *src, const int *src_idx, fpc_tuple *ring0, fpc_tuple *ring1,
+                                                     int cap0, const int *dst_idx, int m) {
+  const int j = blockIdx.x;
+  if (j >= m) return;
+  const int lane = lane_id();
+  const int d = dst_idx[j];
+  const Vec16 *s = reinterpret_cast<const Vec16 *>(src + src_idx[j]);
+  Vec16 *o = reinterpret_cast<Vec16 *>(d < cap0 ? ring0 + d : ring1 + (d - cap0));
+  o[lane] = s[lane];
+  if (lane < 16) o[64 + lane] = s[64 + lane];
+}
+
+// One training sample per workgroup: record ring[slot[i]] -> the trainer's dense row (alphazero.py:71-73, :104-110)
+//   enc[i] [24,R,R]  what k_encode mode 0 writes for a board with this record's sq and turn, rotated by that turn
+//                    (GetEncodedState per tuple: the sample's own rotation), under the engine's current rule set;
+//   pi[i]  [A]       zero but pi[flat[k]] = (float)visits[k] / (float)S for k < n, S = sum of the visits as an integer;
+//                    one IEEE f32 division, so the row has the bits of tuples.dense_pi (S <= 256 * 65535 < 2^24: torch's
+//                    f32 sum is exact in any order).  n == 0 gives an all-zero row where dense_pi gives NaN -- a finished
+//                    search of a live game never leaves such a record.  A flat >= A (never made by a search) is dropped;
+//   z[i]             rec.z.
+// Thread k owns child k (RD_THREADS == FPC_TUPLE_MAXC).  Both rows leave as 16-byte stores, lane after lane (enc and pi
+// rows start on 16-byte boundaries: 24*RR and A = 8(R+1)RR are multiples of 4 floats).  The at most 256 nonzeros of pi
+// are 4-byte stores into the row this workgroup has just zeroed, ordered behind the zero fill by the barrier
+// (k_mask_from_moves' idiom); they merge in L2 with the lines the fill left there.
+constexpr int RD_THREADS = 256;
+static_assert(RD_THREADS == FPC_TUPLE_MAXC && RD_THREADS >= FPC_MAX_SQ, "k_replay_decode: one thread per child, one per square");
+__global__ void __launch_bounds__(RD_THREADS) k_replay_decode(DevCfg c, const fpc_tuple *ring, const int *slot, int n,
+                                                              float *enc, float *pi, float *z) {
+  __shared__ int8_t s_plane[FPC_MAX_SQ];           // input plane of the piece on each square of the rotated board, -1 empty
+  __shared__ int s_sum[RD_THREADS / 64];
+  const int i = blockIdx.x;
+  if (i >= n) return;
+  const int tid = (int)threadIdx.x;
+  const fpc_tuple *rec = ring + slot[i];
+  const int R = c.R, RR = c.RR, turn = rec->turn & 3;
+  if (tid < RR) {
+    const int row = row_of(c, tid);
+    const uint8_t p = rec->sq[rot90_src(R, turn, row, tid - row * R)];
+    s_plane[tid] = (int8_t)(present(p) ? piece_plane(p, turn, c.rules) : -1);
+  }
+  const int nc = rec->n < FPC_TUPLE_MAXC ? (int)rec->n : FPC_TUPLE_MAXC;
+  const int flat = tid < nc ? (int)rec->flat[tid] : 0;
+  const int vis = tid < nc ? (int)rec->visits[tid] : 0;
+  int s = vis;
+  for (int m = 32; m; m >>= 1) s += __shfl_xor(s, m);
+  if ((tid & 63) == 0) s_sum[tid >> 6] = s;
+  __syncthreads();
+  const int S = s_sum[0] + s_sum[1] + s_sum[2] + s_sum[3];
+  if (tid == 0) z[i] = rec->z;
+  float4 *e4 = reinterpret_cast<float4 *>(enc + (size_t)i * 24 * RR);
+  // (plane, square) of a piece's first float, carried from piece to piece: one division per thread, none per piece
+  const int dplane = (4 * RD_THREADS) / RR, dpos = 4 * RD_THREADS - dplane * RR;
+  int plane0 = (4 * tid) / RR, pos0 = 4 * tid - plane0 * RR;
+  for (int q = tid; q < 6 * RR; q += RD_THREADS) {
+    int plane = plane0, pos = pos0;                         // a 16-byte piece may straddle two planes (RR odd)
+    float o[4];
+    for (int j = 0; j < 4; ++j) {
+      o[j] = s_plane[pos] == plane ? 1.0f : 0.0f;
+      if (++pos == RR) { pos = 0; ++plane; }
+    }
+    float4 v;
+    v.x = o[0]; v.y = o[1]; v.z = o[2]; v.w = o[3];
+    e4[q] = v;
+    plane0 += dplane;
+    pos0 += dpos;
+    if (pos0 >= RR) { pos0 -= RR; ++plane0; }
+  }
+  float *prow = pi + (size_t)i * c.A;
+  float4 *p4 = reinterpret_cast<float4 *>(prow);
+  float4 zero;
+  zero.x = zero.y = zero.z = zero.w = 0.0f;
+  const bool has = tid < nc && flat < c.A;
+  const float val = (float)vis / (float)S;
+  for (int q = tid; q < (c.A >> 2); q += RD_THREADS) p4[q] = zero;
+  __syncthreads();
+  if (has) prow[flat] = val;
 }
 
 // ================================================================================================

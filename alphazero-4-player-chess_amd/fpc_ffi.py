@@ -15,6 +15,7 @@ LIB_PATH = os.environ.get("FPC_ENGINE_LIB") or os.path.join(HERE, "csrc", "libfp
 
 MAX_SQ, MAX_PL, NO_SQ, MAX_MOVES = 196, 16, 255, 256
 MAX_LEAVES = 8                          # FPC_MAX_LEAVES: leaves per game per step of a leaf-parallel search
+REPLAY_RINGS, REPLAY_SCRATCH, REPLAY_COLLECTED, REPLAY_GATHERED = 2, 2, 0, 1     # FPC_REPLAY_*: ring 0 experience, 1 validation
 RULES_STRICT, RULES_PUCT, RULES_ROTATION, RULES_PLANES, RULES_FULL_MOVES, RULES_FIXED = 0, 1, 2, 4, 8, 15
 
 
@@ -130,6 +131,7 @@ _SIGS = {
     "fpc_set_timing": (C.c_int, [C.c_void_p, C.c_int]),
     "fpc_set_policy_mode": (C.c_int, [C.c_void_p, C.c_int]),
     "fpc_stream": (C.c_void_p, [C.c_void_p]),
+    "fpc_memory_is_host": (C.c_int, []),
     "fpc_set_rules": (C.c_int, [C.c_void_p, C.c_int]),
     "fpc_search_set_root_noise": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_float]),
     "fpc_search_set_leaves": (C.c_int, [C.c_void_p, C.c_int, C.c_double]),
@@ -148,6 +150,13 @@ _SIGS = {
     "fpc_debug_comm_fault": (C.c_int, [C.c_void_p, C.c_int]),
     "fpc_boards_attack_maps": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "fpc_gathered_read": (C.c_int, [C.c_void_p, P(Tuple), C.c_int, C.c_int]),
+    "fpc_replay_reserve": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "fpc_replay_push": (C.c_int, [C.c_void_p, C.c_int, P(C.c_int), P(C.c_int8), C.c_int]),
+    "fpc_replay_load": (C.c_int, [C.c_void_p, C.c_int, P(Tuple), C.c_int]),
+    "fpc_replay_size": (C.c_int, [C.c_void_p, C.c_int]),
+    "fpc_replay_read": (C.c_int, [C.c_void_p, C.c_int, P(Tuple), C.c_int, C.c_int]),
+    "fpc_replay_batch": (C.c_int, [C.c_void_p, C.c_int, P(C.c_int), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fpc_replay_decode_ms": (C.c_int, [C.c_void_p, P(C.c_float)]),
 }
 EXPORTS = sorted(_SIGS)
 
@@ -241,6 +250,9 @@ class Engine:
             raise RuntimeError("fpc_create failed (%d): %s" % (rc, (self.L.fpc_last_error(None) or b"").decode()))
         self.h = h
         self.G = 0
+        self.host_memory = bool(self.L.fpc_memory_is_host())   # the emulator build: "device" pointers are host memory
+        self.replay_cap = [0] * (REPLAY_SCRATCH + 1)            # capacity of each replay ring (replay_reserve)
+        self.replay_gen = [0] * (REPLAY_SCRATCH + 1)            # how often each ring has been reserved, i.e. emptied
 
     def close(self):
         if getattr(self, "h", None):
@@ -522,6 +534,70 @@ class Engine:
         """(per-rank counts, ctypes array of all tuples in rank order, total)"""
         counts, total = self.allgather_tuples_device()
         return counts, self.gathered_read(total), total
+
+    # ---- device-resident replay (include/fpc_engine.h fpc_replay_*) ----
+    def replay_reserve(self, ring, capacity):
+        """(re)allocate and empty one ring of `capacity` records in device memory (1280 B each)"""
+        self._chk(self.L.fpc_replay_reserve(self.h, int(ring), int(capacity)))
+        self.replay_cap[ring] = int(capacity)
+        self.replay_gen[ring] += 1
+
+    def replay_push(self, source=REPLAY_COLLECTED, src_index=None, ring_of=None, m=None):
+        """append source tuples src_index[j] (None: 0..m-1) to ring ring_of[j] (None: ring 0; -1: dropped), j in order,
+        device to device.  source: REPLAY_COLLECTED (index space of tuples_read) or REPLAY_GATHERED (gathered_read)."""
+        si = None if src_index is None else np.ascontiguousarray(src_index, np.int32)
+        ro = None if ring_of is None else np.ascontiguousarray(ring_of, np.int8)
+        if m is None:
+            m = si.shape[0] if si is not None else ro.shape[0] if ro is not None else self.tuples_count()
+        assert (si is None or si.shape == (m,)) and (ro is None or ro.shape == (m,))
+        self._chk(self.L.fpc_replay_push(self.h, int(source), None if si is None else C.cast(si.ctypes.data, P(C.c_int)),
+                                         None if ro is None else C.cast(ro.ctypes.data, P(C.c_int8)), int(m)))
+
+    def replay_load(self, ring, arr, n=None):
+        """append n records of a ctypes fpc_tuple array from host memory (resume, tests)"""
+        n = len(arr) if n is None else n
+        self._chk(self.L.fpc_replay_load(self.h, int(ring), arr, int(n)))
+
+    def replay_size(self, ring):
+        n = self.L.fpc_replay_size(self.h, int(ring))
+        if n < 0:
+            self._chk(n)
+        return n
+
+    def replay_read(self, ring, first=0, n=None):
+        """(ctypes fpc_tuple array, n): slots first .. first+n-1 of the ring (default: all of it)"""
+        n = self.replay_size(ring) - first if n is None else n
+        arr = (Tuple * max(n, 1))()
+        self._chk(self.L.fpc_replay_read(self.h, int(ring), arr, int(first), int(n)))
+        return arr, n
+
+    def replay_batch(self, ring, slots, enc, pi, z):
+        """decode the records in `slots` (any order, repeats allowed) into enc [n,24,R,R], pi [n,A], z [n] (f32, device
+        memory; on the emulator, host memory): contiguous torch tensors / numpy arrays, or raw pointers.  One launch;
+        the engine's stream is synchronised before this returns."""
+        sl = np.ascontiguousarray(slots, np.int32)
+        n = int(sl.shape[0])
+        ptrs = []
+        for t, shape in ((enc, (n, 24, self.R, self.R)), (pi, (n, self.A)), (z, (n,))):
+            if isinstance(t, int):
+                ptrs.append(t)
+                continue
+            if isinstance(t, np.ndarray):
+                assert t.dtype == np.float32 and t.flags.c_contiguous and t.size == int(np.prod(shape)), shape
+                ptrs.append(t.ctypes.data)
+            else:
+                assert str(t.dtype) == "torch.float32" and t.is_contiguous() and t.numel() == int(np.prod(shape)), shape
+                ptrs.append(t.data_ptr())
+        if (ptrs[0] | ptrs[1]) & 15:
+            raise ValueError("replay_batch: enc and pi must start on a 16-byte boundary (the kernel writes 16-byte pieces); "
+                             "a sliced view with an odd storage offset does not -- pass a tensor of its own")
+        self._chk(self.L.fpc_replay_batch(self.h, int(ring), C.cast(sl.ctypes.data, P(C.c_int)), n, *ptrs))
+
+    def replay_decode_ms(self):
+        """HIP-event time of k_replay_decode in the last replay_batch (set_timing(True) first)"""
+        ms = C.c_float()
+        self._chk(self.L.fpc_replay_decode_ms(self.h, C.byref(ms)))
+        return ms.value
 
 
 def board_from_dict(R, turn, entries, castle=None, _lib=None):

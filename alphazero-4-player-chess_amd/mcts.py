@@ -151,7 +151,7 @@ class MCTS:
     def _search_external(self, eng, G, sims):
         dev = str(getattr(self.neural_net, "device", "cpu"))
         on_gpu = dev.startswith("cuda") or dev == "gpu"
-        host_engine = not torch.cuda.is_available()    # only true for the test-suite's emulator build
+        host_engine = eng.host_memory                  # only true for the test-suite's emulator build
         R, A = eng.R, eng.A
         keep = None
         # leaf-parallel: ceil(sims / K) steps of K leaves per game, the last one of the remainder (set before the

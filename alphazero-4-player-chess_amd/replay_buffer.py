@@ -1,5 +1,5 @@
 """Ring replay buffer of training tuples (counterpart of the reference's src/py/replay_buffer.py:4-20:
-fixed capacity, overwrite-oldest, uniform sampling without replacement)."""
+fixed capacity, overwrite-oldest, uniform sampling without replacement), and its device-resident form."""
 import random
 
 
@@ -22,3 +22,43 @@ class ReplayBuffer:
 
     def __len__(self):
         return len(self._items)
+
+
+class DeviceReplayBuffer:
+    """The same ring kept in device memory as fpc_tuple records (include/fpc_engine.h fpc_replay_*): ring 0 or 1 of
+    `engine`, filled by Engine.replay_push / replay_load.  sample() draws the positions ReplayBuffer.sample draws from a
+    buffer of the same length (random.sample picks by position from the population size alone) and decodes them in one
+    kernel launch: (x [n,24,R,R], pi [n,A], z [n,1]) f32 on `device` (None: host memory, the emulator backend).
+    An engine has one ring of each number: making a second buffer on the same engine and ring empties the ring under the
+    first one, whose next use then raises."""
+
+    def __init__(self, engine, ring, capacity, rng=None, device=None):
+        self.eng, self.ring, self.capacity = engine, int(ring), int(capacity)
+        self._rng = rng or random
+        self.device = device
+        engine.replay_reserve(self.ring, self.capacity)
+        self._gen = engine.replay_gen[self.ring]
+
+    def _mine(self):
+        if self.eng.replay_gen[self.ring] != self._gen:
+            raise RuntimeError("DeviceReplayBuffer: ring %d of this engine has been reserved again since this buffer was made "
+                               "(another buffer on the same engine?): its contents are gone" % self.ring)
+
+    def __len__(self):
+        self._mine()
+        return self.eng.replay_size(self.ring)
+
+    def decode(self, slots):
+        import torch
+        self._mine()
+        n, e = len(slots), self.eng
+        kw = {"dtype": torch.float32, "device": self.device if self.device is not None else "cpu"}
+        x, pi, z = torch.empty((n, 24, e.R, e.R), **kw), torch.empty((n, e.A), **kw), torch.empty((n, 1), **kw)
+        if n:
+            if self.device is not None:
+                torch.cuda.current_stream(self.device).synchronize()    # the allocator may hand out blocks queued work still reads
+            e.replay_batch(self.ring, slots, x, pi, z)
+        return x, pi, z
+
+    def sample(self, batch_size):
+        return self.decode(self._rng.sample(range(len(self)), batch_size))

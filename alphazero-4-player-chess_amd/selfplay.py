@@ -42,7 +42,7 @@ class Episode:
         self.length = 0
 
 
-def play(search_fn, eng, start_boards, args, uniforms, continue_fn=None):
+def play(search_fn, eng, start_boards, args, uniforms, continue_fn=None, on_searched=None):
     """search_fn(list_of_PODs) -> search_results dict (fpc_ffi.Engine.search_results layout) and
     leaves the PODs with the piece-list order the search produced.  uniforms[ply][gid] in [0,1).
     continue_fn (opt-in subtree reuse, not reference semantics; None: every ply is search_fn, as in the reference):
@@ -50,6 +50,8 @@ def play(search_fn, eng, start_boards, args, uniforms, continue_fn=None):
     indices, within the last batch, of the games that go on (ascending), picks_of_kept: the moves they played; it
     re-roots the last search on those moves (fpc_search_advance), searches, overwrites `states` with the trees' root
     PODs and returns the same dict.  Terminal detection stays here, on this loop's own copies of the states.
+    on_searched (optional): called as on_searched(ids, ply) right after each ply's search has returned, ids = the game
+    ids of that search in batch order (AlphaZero's device replay collects the ply's tuples on the device there).
     Returns the list of finished Episodes (all games, in game-id order)."""
     R = eng.R
     states = [fpc_ffi.clone_board(b) for b in start_boards]
@@ -60,6 +62,8 @@ def play(search_fn, eng, start_boards, args, uniforms, continue_fn=None):
         if not states:
             break
         res = search_fn(states) if continue_fn is None or ply == 0 else continue_fn(keep_pos, keep_picks, states)
+        if on_searched is not None:
+            on_searched(list(ids), ply)
         picks = []
         for i in range(len(states)):
             n = int(res["n_children"][i])

@@ -185,3 +185,34 @@ def dense_batch(eng, recs):
     pi = torch.stack([dense_pi(r, eng.A) for r in recs]) if recs else torch.zeros(0, eng.A)
     z = torch.tensor([r["z"] for r in recs], dtype=torch.float32).view(-1, 1)
     return torch.from_numpy(enc), pi, z
+
+
+def tuples_of(recs):
+    """list of record dicts (records_of / unpack_records layout) -> ctypes fpc_tuple array"""
+    arr = (fpc_ffi.Tuple * max(len(recs), 1))()
+    for t, r in zip(arr, recs):
+        mb = np.asarray(r["mailbox"], np.uint8)
+        C.memmove(t.sq, mb.ctypes.data, mb.shape[0])
+        t.turn, t.n, t.z = int(r["turn"]), len(r["flat"]), float(r["z"])
+        t.game, t.ply = int(r.get("game", 0)), int(r.get("ply", 0))
+        fv = np.zeros((2, fpc_ffi.MAX_TUPLE_C), np.uint16)
+        fv[0, :t.n], fv[1, :t.n] = r["flat"], r["visits"]
+        C.memmove(t.flat, fv[0].ctypes.data, 2 * fpc_ffi.MAX_TUPLE_C)
+        C.memmove(t.visits, fv[1].ctypes.data, 2 * fpc_ffi.MAX_TUPLE_C)
+    return arr
+
+
+def dense_batch_device(eng, recs, device="cuda"):
+    """dense_batch's three tensors, bit for bit, left on `device` (None: host memory, the emulator backend) by one upload
+    of the records and one decode launch on the engine's scratch ring (fpc_replay_load + fpc_replay_batch)"""
+    n = len(recs)
+    kw = {"dtype": torch.float32, "device": device if device is not None else "cpu"}
+    enc, pi, z = torch.empty((n, 24, eng.R, eng.R), **kw), torch.empty((n, eng.A), **kw), torch.empty((n, 1), **kw)
+    if n:
+        # the scratch ring only grows: its current capacity again empties it without touching the allocation
+        eng.replay_reserve(fpc_ffi.REPLAY_SCRATCH, max(n, eng.replay_cap[fpc_ffi.REPLAY_SCRATCH]))
+        eng.replay_load(fpc_ffi.REPLAY_SCRATCH, tuples_of(recs), n)
+        if device is not None:
+            torch.cuda.current_stream(device).synchronize()
+        eng.replay_batch(fpc_ffi.REPLAY_SCRATCH, np.arange(n), enc, pi, z)
+    return enc, pi, z

@@ -278,6 +278,34 @@ int fpc_allgather_tuples(fpc_engine *e, int *counts_out, int *total_out);
 int fpc_debug_comm_fault(fpc_engine *e, int point);
 int fpc_gathered_read(fpc_engine *e, fpc_tuple *host_out, int first, int n);
 
+/* ---- device-resident replay: the trainer's two ring buffers (alphazero.py:33-34, replay_buffer.py:4-20) as fpc_tuple
+ * arrays in device memory, 1280 B per record, and one launch (k_replay_decode) that turns any selection of slots into the
+ * dense batch the optimiser step reads.  Ring semantics are replay_buffer.ReplayBuffer's: append until `capacity`, then
+ * overwrite at a cursor that advances modulo capacity; slot i is the i-th element of that buffer's list.  The cursors
+ * live on the host.
+ * FPC_EINVAL: ring outside 0..FPC_REPLAY_SCRATCH, capacity < 1, null or (fpc_replay_batch) not 16-byte aligned outputs,
+ * n or m < 0, a slot outside 0..size-1, a src_index outside the source's count, a ring_of outside -1..FPC_REPLAY_RINGS-1;
+ * FPC_ESTATE: push, load or batch on a ring never reserved, FPC_REPLAY_GATHERED before any fpc_allgather_tuples;
+ * FPC_ENOMEM: allocation failure.  A call that fails on its arguments leaves every ring as it was. */
+#define FPC_REPLAY_RINGS 2              /* 0 experience, 1 validation */
+#define FPC_REPLAY_SCRATCH 2            /* a third ring for reserve / load / read / batch only (tuples.dense_batch_device): never a push target */
+enum { FPC_REPLAY_COLLECTED = 0,        /* source: this engine's collected tuples, index space of fpc_tuples_read */
+       FPC_REPLAY_GATHERED = 1 };       /* source: the last fpc_allgather_tuples, index space of fpc_gathered_read (padding is never copied) */
+int fpc_replay_reserve(fpc_engine *e, int ring, int capacity);   /* (re)allocate and empty one ring; its current capacity again only
+                                                                  * empties it; on FPC_ENOMEM the ring and its contents are as they were */
+/* j = 0..m-1 in order: source tuple src_index[j] (NULL: j) is appended to ring ring_of[j] (NULL: ring 0; -1: dropped).
+ * Device to device, one k_replay_store launch per call; of several entries landing on one slot only the last is copied. */
+int fpc_replay_push(fpc_engine *e, int source, const int *src_index, const int8_t *ring_of, int m);
+int fpc_replay_load(fpc_engine *e, int ring, const fpc_tuple *host, int n);   /* append n records from host memory (resume, tests) */
+int fpc_replay_size(fpc_engine *e, int ring);
+int fpc_replay_read(fpc_engine *e, int ring, fpc_tuple *host_out, int first_slot, int n);
+/* The batch of the records in slot[0..n-1] (host array; any order, repeats allowed), written to DEVICE memory:
+ * enc_dev [n,24,R,R] f32 = GetEncodedState of each record by its own side to move (alphazero.py:71-73) under the engine's
+ * current rule set, pi_dev [n,A] f32 = visits / sum(visits) at the record's flat indices and 0 elsewhere (bit-identical to
+ * the host path's torch arithmetic; a record with n == 0 gives a zero row), z_dev [n] f32.  Launched on the engine's
+ * stream, which is synchronised before the call returns: any other stream may read the outputs afterwards. */
+int fpc_replay_batch(fpc_engine *e, int ring, const int *slot, int n, float *enc_dev, float *pi_dev, float *z_dev);
+
 /* ---- measurement hooks (bench.py) -------------------------------------------------------- */
 typedef struct fpc_stats {
   /* HIP-event time (events recorded on the engine's stream, resolved in fpc_search_results)
@@ -295,7 +323,11 @@ int fpc_set_timing(fpc_engine *e, int enabled);  /* HIP events around each stage
 const char *fpc_nn_kernel(fpc_engine *e);        /* name of the kernel that runs the residual tower for the loaded weights:
                                                   * "k_towerw" (hidden 256; hidden 128 off the 14x14 board), "k_towerc" (hidden 128, 14x14: k_tower's
                                                   * skeleton on the compact image), "k_tower" (developer knobs), "k_conv3x3" (per layer), "" before fpc_load_weights */
+/* HIP-event time of k_replay_decode alone in the last fpc_replay_batch that ran with fpc_set_timing on (else FPC_ESTATE) */
+int fpc_replay_decode_ms(fpc_engine *e, float *ms_out);
 void *fpc_stream(fpc_engine *e);                 /* hipStream_t the engine launches on */
+int fpc_memory_is_host(void);                    /* 1 in the wavefront-emulator build of these sources, where every "device" pointer
+                                                  * (enc_dev, logits_dev, the fpc_replay_batch outputs, ...) is host memory; 0 in the product */
 
 #ifdef __cplusplus
 }
