@@ -1,7 +1,9 @@
 """tests/tower_probe.py proven able to fail, without a GPU: the comparators of test_tower_probe_gpu.py are fed the
 reference's own output with one layer mutated the way a tap-loop rewrite goes wrong, and must flag every mutation in
 both weight families; the fp32-order reference must pass; family A's input conditions hold for every GPU case; the
-spliced weight blob is the exported one."""
+spliced weight blob is the exported one.  The dense integer Linear of tests/test_linear_probe_gpu.py likewise: its blob
+read back with numpy alone, its exactness condition for every GPU case, NO fragment product of its inputs dead, and five
+faults of the Linear's own decomposition flagged."""
 import copy
 
 import numpy as np
@@ -146,3 +148,83 @@ def test_spliced_blob_is_the_exported_blob(dtype, layout):
     width = tp.set_tower_probe(pm, 56)
     out = tp.forward(tp.conv_layers(pm, dtype), tp.probe_inputs(R, 9), dtype)
     assert width == 72 and np.array_equal(out["policy"], out["tower"][:, 56:128])
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the dense integer Linear (tests/test_linear_probe_gpu.py)
+# ---------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("R", [8, 9])
+@pytest.mark.parametrize("layout", [2, 1])
+def test_dense_linear_blob_round_trip(R, layout):
+    """the exported "dense_int" Linear with the fragment order [k32][n-tile][lane = 16 q + c][8] and the NCHW -> NHWC input
+    permutation undone by numpy: W itself, zeros in ALL padding (9x9 pads Np and Kp under both layouts), the bias --
+    byte for byte"""
+    W, bias = tp.dense_weights(R)
+    A = W.shape[0]
+    for dtype in (1, 0):
+        t = tp.tail(R, dtype, layout, "dense_int")
+        gw = 384 if layout == 2 else 256
+        assert (t.Np, t.Kp) == ((A + gw - 1) // gw * gw, (A + 511) // 512 * 512)
+        if R == 9:
+            assert t.Np > A and t.Kp > A
+        w, b = tp.decode_linear(t)
+        assert np.array_equal(w[:A, :A], tp.engine_order(W, R).astype(np.float32))
+        raw = np.frombuffer(t.bytes, np.uint16, t.Np * t.Kp).reshape(t.Kp // 32, t.Np // 16, 4, 16, 8).transpose(1, 3, 0, 2, 4).reshape(t.Np, t.Kp)
+        assert not raw[A:].any() and not raw[:, A:].any()                      # padding: zero BITS, not just zero values
+        assert b.tobytes() == np.concatenate([bias.astype(np.float32), np.zeros(t.Np - A, np.float32)]).tobytes()
+        assert np.abs(bias).max() == 5 and np.abs(W).max() == 3
+
+
+def test_dense_linear_scaled_tail_is_exact():
+    """ "dense_scaled": W and bias times 2^-s survive the rounding to either operand type; the value Linear is zero"""
+    R, s = 8, 9
+    W, bias = tp.dense_weights(R)
+    A = W.shape[0]
+    for dtype in (1, 0):
+        t = tp.tail(R, dtype, 2, "dense_scaled", s=s)
+        w, b = tp.decode_linear(t)
+        assert np.array_equal(w[:A, :A].astype(np.float64) * 2.0 ** s, tp.engine_order(W, R).astype(np.float64))
+        assert np.array_equal(b[:A].astype(np.float64) * 2.0 ** s, bias.astype(np.float64))
+        assert not np.frombuffer(t.bytes, np.uint8, offset=2 * t.Np * t.Kp + 4 * t.Np).any()     # value Linear and bias: 0
+
+
+@pytest.mark.parametrize("key", sorted(set((c[0], c[1], max(c[3])) for c in tp.LINEAR_CASES)),
+                         ids=lambda k: "%dx%d-%s-%d" % (k[0], k[0], tp.FMT[k[1]]["name"], k[2]))
+def test_dense_linear_exactness_holds_for_every_gpu_case(key):
+    """max_row sum|x| * max|w| + max|bias| < 2^24 (and family A's conditions, inside prepare) for every case of the GPU
+    table: fp32 accumulation of these logits is exact in any order"""
+    R, dtype, rows = key
+    p = tp.prepare(tp.linear_case(R, dtype, rows))
+    W, bias = tp.dense_weights(R)
+    lhs = tp.linear_conditions(p["ref"]["policy"].reshape(rows, -1), W, bias)
+    print("%dx%d %s %d rows: sum|x| max|w| + max|b| = %.0f = 2^%.2f" % (R, R, tp.FMT[dtype]["name"], rows, lhs, np.log2(lhs)))
+
+
+@pytest.mark.parametrize("R,dtype", [(8, 1), (8, 0), (14, 1)], ids=["8x8-fp16", "8x8-bf16", "14x14-fp16"])
+def test_no_fragment_product_of_the_dense_linear_is_dead(R, dtype):
+    """What keeps the bit-for-bit test from hiding a failure: for the 256-row inputs EVERY (16-row tile, 16-column tile,
+    32-deep k-step) contribution block X[16, 32] . W[16, 32]^T is nonzero somewhere -- the allowed share of dead triples
+    is 0 -- so a fragment product dropped, doubled or put in the wrong place changes a logit.  The same for the row
+    the 1-row forward runs, per (column tile, k-step)."""
+    p = tp.prepare(tp.linear_case(R, dtype, 256))
+    policy = p["ref"]["policy"]
+    dead, total = tp.dead_fragment_products(policy, R)
+    A = policy[0].size
+    assert total == 16 * (A // 16) * ((A + 31) // 32)
+    assert dead == 0, (dead, total)
+    dead1, total1 = tp.dead_fragment_products(policy[tp.linear_rows(256, 1)], R, row_tiles=False)
+    assert total1 == total // 16 and dead1 == 0, (dead1, total1)
+
+
+@pytest.mark.parametrize("layout", [2, 1])
+@pytest.mark.parametrize("dtype", [1, 0], ids=["fp16", "bf16"])
+def test_every_linear_mutation_is_flagged(dtype, layout):
+    """the reference Linear with one fault of the kernels' own decomposition, at 8x8 with 256 rows: check_exact must raise"""
+    R = 8
+    p = tp.prepare(tp.linear_case(R, dtype, 256))
+    want = tp.dense_reference(p, R)
+    tp.check_exact(want.astype(np.float32), want, "the reference itself")
+    for name in tp.LINEAR_MUTATIONS:
+        bad = tp.mutated_logits(p["ref"]["policy"], R, layout, name)
+        with pytest.raises(AssertionError):
+            tp.check_exact(bad.astype(np.float32), want, name)

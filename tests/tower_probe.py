@@ -410,46 +410,80 @@ def permutation(R, seed=7):
     return rng.permutation(A), (rng.choice([-1.0, 1.0], size=A) * np.exp2(rng.integers(-2, 3, size=A))).astype(np.float32)
 
 
+def dense_weights(R):
+    """the dense integer Linear: (W int8 [A, A] in {-3..3}, indexed [out, in] in the reference's NCHW input order, bias
+    int64 [A] in {-5..5}), both from ONE generator.  Plain random draws, no structure: any two columns differ, so a
+    swap of two of them shows.  Kept as int8 (553 MB at 14x14); of the large ones only the last stays cached."""
+    if R not in _dense:
+        if R >= 12:
+            for k in [k for k in _dense if k >= 12]:
+                _dense.pop(k)
+        A = (8 * R + 8) * R * R
+        rng = np.random.default_rng(1000 + R)
+        W = rng.integers(-3, 4, size=(A, A), dtype=np.int8)
+        _dense[R] = (W, rng.integers(-5, 6, size=A))
+    return _dense[R]
+
+
+_dense = {}
+DENSE = ("dense_int", "dense_scaled")
+
+
 class Tail:
-    """the Linear sections of an exported blob and the header words that describe them"""
-    def __init__(self, R, dtype, layout, kind):
+    """the Linear sections of an exported blob and the header words that describe them.  kind: "identity" | "perm" |
+    "dense_int" (dense_weights, value Linear = value_vector) | "dense_scaled" (dense_weights times 2^-s, exact in both
+    operand types; the value Linear all zero, so the value is tanh(0))"""
+    def __init__(self, R, dtype, layout, kind, s=0):
         A_ch, RR = 8 * R + 8, R * R
         A = A_ch * RR
+        assert kind in ("identity", "perm") + DENSE and (s == 0 or kind == "dense_scaled")
         m = net.ResNet(stub_spec(R), 0, 64, "cpu")
         fc = torch.nn.utils.skip_init(torch.nn.Linear, A, A)
         with torch.no_grad():
-            fc.weight.zero_()
-            fc.bias.zero_()
-            if kind == "identity":
-                fc.weight.diagonal().fill_(1.0)
-            else:
-                perm, scale = permutation(R)
-                fc.weight[torch.arange(A), torch.from_numpy(perm)] = torch.from_numpy(scale)
             vfc = torch.nn.Linear(24 * RR, 1)
             vw, vb = value_vector(R)
             vfc.weight.copy_(torch.from_numpy(vw).view(1, -1))
             vfc.bias.fill_(float(vb))
+            if kind in DENSE:
+                W, bias = dense_weights(R)
+                fc.weight.copy_(torch.from_numpy(W))
+                fc.bias.copy_(torch.from_numpy(bias))
+                if kind == "dense_scaled":
+                    assert 0 <= s <= 12                           # 3 * 2^-s: a normal number of both operand types
+                    fc.weight.mul_(2.0 ** -s)
+                    fc.bias.mul_(2.0 ** -s)
+                    vfc.weight.zero_()
+                    vfc.bias.zero_()
+                del W
+            else:
+                fc.weight.zero_()
+                fc.bias.zero_()
+                if kind == "identity":
+                    fc.weight.diagonal().fill_(1.0)
+                else:
+                    perm, scale = permutation(R)
+                    fc.weight[torch.arange(A), torch.from_numpy(perm)] = torch.from_numpy(scale)
         m.policyHead[4], m.valueHead[4] = fc, vfc
         blob = weights.export_weights(m.eval(), dtype, fc_layout=layout)
         del m, fc
         magic, version, r, F, nb, dt, a_ch, self.Np, self.Kp, lay = struct.unpack_from("<4s9i", blob, 0)
         assert (magic, version, r, F, nb, dt, a_ch, lay) == (b"FPCW", 3, R, 64, 0, dtype, A_ch, layout)
-        self.R, self.dtype, self.layout, self.kind = R, dtype, layout, kind
+        self.R, self.dtype, self.layout, self.kind, self.s = R, dtype, layout, kind, s
         self.bytes = blob[head_len(64, 0):]
 
 
 _tails = {}
 
 
-def tail(R, dtype, layout, kind, keep=2):
-    """one exported Linear per (board, operand type, layout, kind); of the large ones (1.1 GB each at 14x14) only the
-    last `keep` stay cached"""
-    key = (R, dtype, layout, kind)
+def tail(R, dtype, layout, kind, keep=2, s=0):
+    """one exported Linear per (board, operand type, layout, kind, scale exponent); of the large ones (1.1 GB each at
+    14x14) only the last `keep` stay cached"""
+    key = (R, dtype, layout, kind) + ((s,) if s else ())
     if key not in _tails:
         big = [k for k in _tails if k[0] >= 12]
-        if R >= 12 and len(big) >= keep:
-            _tails.pop(big[0])
-        _tails[key] = Tail(R, dtype, layout, kind)
+        while R >= 12 and len(big) >= keep:
+            _tails.pop(big.pop(0))
+        _tails[key] = Tail(R, dtype, layout, kind, s)
     return _tails[key]
 
 
@@ -462,13 +496,187 @@ def splice(m, t):
     return struct.pack("<4s9i24x", b"FPCW", 3, t.R, F, nb, t.dtype, a_ch, t.Np, t.Kp, t.layout) + cb[64:hl] + t.bytes
 
 
-def expected_logits(policy, kind, R):
+def dense_apply(flat, W, bias, block=1024):
+    """flat @ W.T + bias in float64, W (int8) converted one block of output columns at a time: no A x A matrix wider
+    than int8 ever exists"""
+    x = torch.from_numpy(np.ascontiguousarray(flat, np.float64))
+    A = W.shape[0]
+    out = torch.empty(flat.shape[0], A, dtype=torch.float64)
+    Wt = torch.from_numpy(W)
+    # ONE conversion buffer, refilled block after block: at 14x14 the int8 -> float64 conversion of 553 M elements is most
+    # of a call (one call per search step), and into fresh memory it costs three times as much
+    buf = torch.empty(min(block, A), A, dtype=torch.float64)
+    for c in range(0, A, block):
+        n = min(block, A - c)
+        buf[:n].copy_(Wt[c:c + n])
+        out[:, c:c + n] = x @ buf[:n].t()
+    out = out.numpy()
+    return out + np.asarray(bias, np.float64)[None, :]
+
+
+def linear_conditions(flat, W, bias):
+    """the dense integer Linear's exactness condition, from the reference alone: integer activations, and
+    max_row sum|x| * max|w| + max|bias| < 2^24 -- then EVERY partial sum of a logit, in any order and any grouping,
+    is an integer below 2^24 and fp32 accumulation is exact (a power-of-two scale of W and bias changes nothing).
+    Returns the left-hand side."""
+    flat = np.asarray(flat, np.float64)
+    assert np.array_equal(flat, np.rint(flat))
+    lhs = float(np.abs(flat).sum(axis=1).max()) * float(np.abs(W).max()) + float(np.abs(bias).max())
+    assert lhs < 2.0 ** 24, ("a partial sum of the dense integer Linear may leave fp32's exact integers", lhs)
+    return lhs
+
+
+def expected_logits(policy, kind, R, s=0):
     """what the probe's logits must be, from the reference's policy-conv output [n, A_ch, R, R] (NCHW flatten)"""
     flat = policy.reshape(policy.shape[0], -1)
     if kind == "identity":
         return flat
+    if kind in DENSE:
+        W, bias = dense_weights(R)
+        return dense_apply(flat, W, bias) * (2.0 ** -s if kind == "dense_scaled" else 1.0)
     perm, scale = permutation(R)
     return flat[:, perm] * scale.astype(np.float64)[None, :] + 0.0
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the dense integer Linear taken apart the way k_fcw / k_fc16 + k_fc_reduce take it apart (csrc/fpc_fc.h): the engine's
+# K order, the blob's fragment order, 16-row x 16-column x 32-deep fragment products, K-split slabs
+# ---------------------------------------------------------------------------------------------------------------------
+def engine_order(a, R):
+    """last axis from the reference's NCHW flatten (ch * R * R + pos) to the engine's NHWC flatten (pos * A_ch + ch)"""
+    A_ch, RR = 8 * R + 8, R * R
+    return np.ascontiguousarray(a.reshape(a.shape[:-1] + (A_ch, RR)).swapaxes(-1, -2)).reshape(a.shape)
+
+
+def decode_linear(t):
+    """the policy Linear of a Tail read back with numpy alone: (W' float32 [Np, Kp] in the engine's K order, bias
+    float32 [Np]) -- the inverse of the blob's fragment order [k-step of 32][column tile of 16][lane = 16 q + c][8],
+    element (ks, nt, q, c, e) = W'[16 nt + c][32 ks + 8 q + e]"""
+    n = t.Np * t.Kp
+    raw = np.frombuffer(t.bytes, np.uint16, n)
+    if t.dtype == 1:
+        v = raw.view(np.float16).astype(np.float32)
+    else:
+        v = (raw.astype(np.uint32) << 16).view(np.float32)
+    w = v.reshape(t.Kp // 32, t.Np // 16, 4, 16, 8).transpose(1, 3, 0, 2, 4).reshape(t.Np, t.Kp)
+    return w, np.frombuffer(t.bytes, np.float32, t.Np, 2 * n)      # Np * Kp * 2 bytes: a multiple of 64, no gap
+
+
+def linear_splits(R, layout):
+    """(columns of a column group, K-splits of column group 0) of a forward of at most 256 rows on a 256-CU part:
+    plan_fcw for layout 2; layout 1 cuts its long blocks -- group 0 is one wherever there is any -- into FC_SPLITK = 4"""
+    return (384, weights.fcw_split(R)) if layout == 2 else (256, 4)
+
+
+LINEAR_MUTATIONS = ("drop_kstep", "seam_twice", "drop_bias4", "drop_last_slab", "rowtile15_next_kstep")
+
+
+def mutated_logits(policy, R, layout, name):
+    """expected_logits(policy, "dense_int", R) with ONE fault of the kind a rewrite of the Linear kernels makes, in the
+    engine's own decomposition (k-steps of 32 in NHWC order, column tiles of 16, K-split slabs per column group)"""
+    W, bias = dense_weights(R)
+    A = W.shape[0]
+    flat = policy.reshape(policy.shape[0], -1)
+    out = dense_apply(flat, W, bias)
+    X, Wp = engine_order(flat, R), engine_order(W, R).astype(np.float64)
+    Kp = (A + 511) // 512 * 512
+    gw, sk = linear_splits(R, layout)
+    klen = Kp // sk                                            # K elements per slab
+    g0, ct, ks = 1, gw // 16 + 5, klen // 32 + 3               # column group 1; a column tile and a k-step inside it
+
+    def part(rows, cols, k0, k1):
+        k1 = min(k1, A)
+        return X[rows, k0:k1] @ Wp[cols, k0:k1].T
+
+    every = slice(0, X.shape[0])
+    if name == "drop_kstep":                                    # one k-step of one column tile never multiplied
+        cols = slice(16 * ct, 16 * ct + 16)
+        out[:, cols] -= part(every, cols, 32 * ks, 32 * ks + 32)
+    elif name == "seam_twice":                                  # the first k-step behind a K-split seam added twice
+        cols = slice(g0 * gw, min((g0 + 1) * gw, A))
+        out[:, cols] += part(every, cols, 2 * klen, 2 * klen + 32)
+    elif name == "drop_bias4":                                  # k_fc_reduce: the bias of one float4 of columns
+        assert np.abs(bias[4 * 301:4 * 301 + 4]).max() > 0
+        out[:, 4 * 301:4 * 301 + 4] -= bias[4 * 301:4 * 301 + 4]
+    elif name == "drop_last_slab":                              # k_fc_reduce / logit_at: one slab short
+        cols = slice(g0 * gw, min((g0 + 1) * gw, A))
+        out[:, cols] -= part(every, cols, (sk - 1) * klen, sk * klen)
+    elif name == "rowtile15_next_kstep":                        # row tile 15 reads the next k-step's activations
+        assert X.shape[0] == 256
+        rows, cols = slice(240, 256), slice(0, A)
+        out[rows] += X[rows, 32 * ks + 32:32 * ks + 64] @ Wp[:, 32 * ks:32 * ks + 32].T - part(rows, cols, 32 * ks, 32 * ks + 32)
+    else:
+        raise ValueError(name)
+    return out
+
+
+def dead_fragment_products(policy, R, row_tiles=True):
+    """(dead, total) over every (16-row tile, 16-column tile, 32-deep k-step) of real indices: a triple is dead when
+    its contribution X[16, 32] . W[16, 32]^T is zero in all 256 elements -- dropping, duplicating or misplacing that
+    fragment product would then change no logit.  row_tiles False: the rows are taken one by one (the 1-row forward),
+    a (row, column tile, k-step) is dead when all 16 elements are zero.  fp32 products of integers: exact."""
+    W, _ = dense_weights(R)
+    A = W.shape[0]
+    X = torch.from_numpy(engine_order(policy.reshape(policy.shape[0], -1), R).astype(np.float32))
+    Wk = torch.from_numpy(np.ascontiguousarray(engine_order(W, R).T))       # [K, N] int8: a k-step is 32 contiguous rows
+    n, nct = X.shape[0], (A + 15) // 16
+    assert not row_tiles or n % 16 == 0
+    assert A % 16 == 0                                          # A = 8 (R + 1) R^2: the column tiles have no ragged end
+    dead = total = 0
+    for k0 in range(0, A, 32):
+        c = X[:, k0:k0 + 32] @ Wk[k0:k0 + 32].to(torch.float32)
+        live = (c != 0).view(n // 16 if row_tiles else n, 16 if row_tiles else 1, nct, 16).any(dim=3).any(dim=1)
+        dead += int((~live).sum())
+        total += live.numel()
+    return dead, total
+
+
+def linear_rows(rows_max, n):
+    """which rows of a case's prepared inputs a forward of n rows takes: the whole set, or a window that does NOT start
+    at row 0 -- whatever an earlier, larger call left in the engine's buffers then belongs to other inputs"""
+    if n == rows_max:
+        return slice(0, n)
+    lo = {37: 64, 1: 128}[n]
+    return slice(lo, lo + n)
+
+
+def linear_case(R, dtype, rows):
+    """the prepare() case of a dense-Linear test: family A, hidden 128, 3 blocks with fp16 / 2 with bf16"""
+    return ("linear", R, 128, 3 if dtype == 1 else 2, dtype, "A", {}, rows)
+
+
+def dense_reference(p, R):
+    """expected dense_int logits of a prepared case, computed once; the exactness condition asserted"""
+    if "dense_int" not in p:
+        W, bias = dense_weights(R)
+        p["linear_lhs"] = linear_conditions(p["ref"]["policy"].reshape(p["x"].shape[0], -1), W, bias)
+        p["dense_int"] = expected_logits(p["ref"]["policy"], "dense_int", R)
+    return p["dense_int"]
+
+
+def _linear_cases():
+    """(R, operand type, layout, row counts run one after the other on ONE engine), ordered so that cases sharing a
+    (board, type) preparation and a (board, type, layout) tail are neighbours"""
+    out = []
+    for R in (8, 9, 10, 11, 12, 13, 14):
+        full = R in (8, 10, 14)
+        seq = (256, 37, 1) if full else (256, 37)
+        for dtype in (1, 0):
+            for layout in (2, 1):
+                if full or dtype == 1 or layout == weights.default_fc_layout(R):
+                    out.append((R, dtype, layout, seq))
+                # two row tiles (blockIdx.y = 1, Mtot = 512): 10x10 layout 1 keeps a long / short mix above 256 rows (the
+                # only shape whose mix CHANGES there), 14x14 layout 1 becomes all-long
+                if dtype == 1 and ((R in (8, 14)) or (R == 10 and layout == 1)):
+                    out.append((R, dtype, layout, (300,)))
+    return out
+
+
+LINEAR_CASES = _linear_cases()
+
+
+def linear_case_id(c):
+    return "%dx%d-%s-layout%d-%s" % (c[0], c[0], FMT[c[1]]["name"], c[2], "-".join(str(n) for n in c[3]))
 
 
 # ---------------------------------------------------------------------------------------------------------------------
