@@ -17,6 +17,10 @@ Same contents, entry for entry, and the same batches, bit for bit, as the host b
 process-wide engine handle, which is therefore sized when this object is made and must not be re-created afterwards,
 and which has one pair of rings: a second AlphaZero with device_replay in the same process takes them over (it empties
 them), and the first one's next use of its buffers raises.
+device_play (default False) -- each ply's moves are drawn, made and judged on the device by one launch
+(fpc_ffi.Engine.search_play on the finished search) instead of a per-game numpy draw and two board-op round trips; the
+draw is selfplay.sample_move's: the inverse CDF over pow(visits, 1/temperature) in f64, which picks sample_action's
+child except within rounding of a boundary.  Composes with reuse_tree and device_replay.
 """
 import numpy as np
 import torch
@@ -64,6 +68,7 @@ class AlphaZero:
         G = int(self.args["num_parallel_games"])
         games = [self._new_game() for _ in range(G)]
         reuse = bool(self.args.get("reuse_tree", False)) if hasattr(self.args, "get") else False
+        device_play = bool(self.args.get("device_play", False)) if hasattr(self.args, "get") else False
         eng = self._engine()
         L = int(self.args["max_game_length"])
         uniforms = torch.rand(L, G, generator=self.gen, dtype=torch.float64).tolist()
@@ -96,7 +101,7 @@ class AlphaZero:
                                    "reconfigured) and the replay rings went with it")
             eng.tuples_reserve(L * G)
         episodes = selfplay.play(search_fn, eng, [g._b for g in games], self.args, uniforms, continue_fn=continue_fn if reuse else None,
-                                 on_searched=on_searched if self.device_replay else None)
+                                 on_searched=on_searched if self.device_replay else None, device_play=device_play)
         split = self.args["replay_buffer_capacity"] / (self.args["replay_buffer_capacity"] + self.args["validation_buffer_capacity"])
         if self.device_replay:
             z_team = np.zeros((2, len(episodes)), np.float32)      # z by (game, team of the side to move), as the Episodes have it

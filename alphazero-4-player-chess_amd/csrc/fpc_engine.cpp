@@ -72,6 +72,14 @@ struct fpc_engine {
   Tree t2{};                      // the second set of node arrays + board pool (only those nine members): k_tree_advance writes
                                   // the re-rooted trees there and the host swaps the two sets; allocated on the first advance
   int *d_adv = nullptr;           // [2][max_games] src_game | flat of one advance
+  // ---- device-side move choice (fpc_search_play); allocated on the first call
+  double *d_powtab = nullptr;     // [max_sims + 16] pow(v, 1 / powtab_T) by the host libm
+  double powtab_T = -1.0;         // temperature the uploaded table was made for (-1: none yet)
+  double *d_play_u = nullptr;     // [max_games] uniforms of one call
+  int *d_play_out = nullptr;      // [3][max_games] flat | result | error bits of one call
+  fpc_board *d_play_next = nullptr;   // [max_games] next states of one call
+  hipEvent_t play_ev[2] = {nullptr, nullptr};   // around k_play_ply while fpc_set_timing is on
+  float play_ms = -1.f;
   // ---- training tuples (device resident until the episode ends) and their RCCL exchange
   fpc_tuple *d_tuples = nullptr;
   int tuple_cap = 0, tuple_count = 0;
@@ -395,6 +403,7 @@ void fpc_destroy(fpc_engine *e) {
   for (void *p : e->allocs) (void)hipFree(p);
   for (auto &ev : e->evpool) if (ev) (void)hipEventDestroy(ev);
   for (auto &ev : e->rp_ev) if (ev) (void)hipEventDestroy(ev);
+  for (auto &ev : e->play_ev) if (ev) (void)hipEventDestroy(ev);
   if (e->stream) (void)hipStreamDestroy(e->stream);
   delete e;
 }
@@ -859,6 +868,59 @@ int fpc_search_advance(fpc_engine *e, const int *src_game, const int *flat, int 
 }
 
 // ------------------------------------------------------------------------------------------------
+// Device-side move choice: what sits between a finished search and fpc_search_advance / the next fpc_search_begin.
+// One k_play_ply launch draws every game's move from its root's visit counts, makes it on a copy of the root state and
+// runs GetGameResult on the result; the host sees two ints (and, if asked, the next state) per game.  The only
+// transcendental of the draw, pow(N, 1/T), is tabulated here with the host libm (as the PUCT log table is in
+// fpc_create) and uploaded when the temperature changes.  Nothing in the tree or in the engine's search state changes.
+int fpc_search_play(fpc_engine *e, double temperature, const double *uniform, int *flat_out, int *result_out, fpc_board *next_out) {
+  if (!e || !uniform || !flat_out || !result_out) return fail(e, FPC_EINVAL, "fpc_search_play: null argument");
+  if (!e->searching || e->stepping) return fail(e, FPC_ESTATE, "fpc_search_play needs a finished search: fpc_search_results has not been read");
+  if (!std::isfinite(temperature) || temperature < 0.0) return fail(e, FPC_EINVAL, "fpc_search_play: temperature must be finite and >= 0 (0: argmax)");
+  const int G = e->G;
+  for (int g = 0; g < G; ++g)
+    if (!(uniform[g] >= 0.0 && uniform[g] < 1.0)) return fail(e, FPC_EINVAL, "fpc_search_play: uniform[%d] = %g is not in [0, 1)", g, uniform[g]);
+  const size_t ntab = (size_t)e->cfg.max_sims + 16;
+  const bool argmax = temperature == 0.0;
+  if (!argmax && !std::isfinite(std::pow((double)(ntab - 1), 1.0 / temperature)))
+    return fail(e, FPC_EINVAL, "fpc_search_play: pow(%zu, 1/%g) is not finite; use temperature 0 for argmax", ntab - 1, temperature);
+  USE_DEV(e);
+  int r;
+  const size_t Gm = (size_t)e->cfg.max_games;
+  if ((!e->d_powtab && (r = dalloc(e, &e->d_powtab, ntab))) || (!e->d_play_u && (r = dalloc(e, &e->d_play_u, Gm))) ||
+      (!e->d_play_out && (r = dalloc(e, &e->d_play_out, 3 * Gm))) || (!e->d_play_next && (r = dalloc(e, &e->d_play_next, Gm))))
+    return r;
+  if (!argmax && temperature != e->powtab_T) {
+    std::vector<double> tab(ntab);
+    for (size_t v = 0; v < ntab; ++v) tab[v] = std::pow((double)v, 1.0 / temperature);
+    e->powtab_T = -1.0;
+    HIPCHK(e, hipMemcpyAsync(e->d_powtab, tab.data(), ntab * sizeof(double), hipMemcpyHostToDevice, e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));     // `tab` goes out of scope
+    e->powtab_T = temperature;
+  }
+  HIPCHK(e, hipMemcpyAsync(e->d_play_u, uniform, (size_t)G * sizeof(double), hipMemcpyHostToDevice, e->stream));
+  int *d_flat = e->d_play_out, *d_res = e->d_play_out + Gm, *d_err = e->d_play_out + 2 * Gm;
+  const bool timed = e->timing;
+  if (timed)
+    for (auto &ev : e->play_ev)
+      if (!ev) HIPCHK(e, hipEventCreate(&ev));
+  if (timed) HIPCHK(e, hipEventRecord(e->play_ev[0], e->stream));
+  FPC_LAUNCH(k_play_ply, G, 64, e->stream, e->dc, e->t, G, (const double *)e->d_powtab, (int)ntab, argmax ? 1 : 0,
+             (const double *)e->d_play_u, d_flat, d_res, e->d_play_next, d_err);
+  HIPCHK(e, hipGetLastError());
+  if (timed) HIPCHK(e, hipEventRecord(e->play_ev[1], e->stream));
+  std::vector<int> errs(G);
+  HIPCHK(e, hipMemcpyAsync(flat_out, d_flat, (size_t)G * sizeof(int), hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(e, hipMemcpyAsync(result_out, d_res, (size_t)G * sizeof(int), hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(e, hipMemcpyAsync(errs.data(), d_err, (size_t)G * sizeof(int), hipMemcpyDeviceToHost, e->stream));
+  if (next_out) HIPCHK(e, hipMemcpyAsync(next_out, e->d_play_next, (size_t)G * sizeof(fpc_board), hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(e, hipStreamSynchronize(e->stream));
+  e->play_ms = -1.f;
+  if (timed) HIPCHK(e, hipEventElapsedTime(&e->play_ms, e->play_ev[0], e->play_ev[1]));
+  return err_to_status(e, errs, "game");
+}
+
+// ------------------------------------------------------------------------------------------------
 int fpc_load_weights(fpc_engine *e, const void *blob, uint64_t nbytes) {
   if (!e || !blob) return fail(e, FPC_EINVAL, "bad argument");
   USE_DEV(e);
@@ -1112,6 +1174,13 @@ int fpc_replay_decode_ms(fpc_engine *e, float *ms_out) {
   if (!e || !ms_out) return fail(e, FPC_EINVAL, "bad argument");
   if (e->rp_decode_ms < 0.f) return fail(e, FPC_ESTATE, "fpc_replay_decode_ms: no fpc_replay_batch has run with fpc_set_timing on");
   *ms_out = e->rp_decode_ms;
+  return 0;
+}
+
+int fpc_search_play_ms(fpc_engine *e, float *ms_out) {
+  if (!e || !ms_out) return fail(e, FPC_EINVAL, "bad argument");
+  if (e->play_ms < 0.f) return fail(e, FPC_ESTATE, "fpc_search_play_ms: no fpc_search_play has run with fpc_set_timing on");
+  *ms_out = e->play_ms;
   return 0;
 }
 

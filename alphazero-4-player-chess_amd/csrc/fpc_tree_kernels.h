@@ -14,6 +14,8 @@
 //   k_select_multi / k_expand(_legal)(_select)_multi  the same for the opt-in leaf-parallel search (K leaves per game
 //                    per step, virtual loss; fpc_search_set_leaves): the descent is select_game's, row k*G + g per leaf
 //   k_tree_advance   opt-in subtree reuse (fpc_search_advance): re-roots every game's tree on the move played, out of place
+//   k_play_ply       opt-in device-side move choice (fpc_search_play): draws each game's move from the finished search's root
+//                    visit counts, makes it on the root state and runs GetGameResult on the result
 //   k_replay_store / k_replay_decode  opt-in device-resident replay (fpc_replay_*): training records into ring slots, and any
 //                    selection of slots into the trainer's dense (state, pi, z) batch in one launch  (alphazero.py:71-73, :104-110)
 //
@@ -252,7 +254,7 @@ __device__ __forceinline__ int wave_list_erase_append(uint8_t *list, int len, in
 // mover's castling rights and a rook leaving its home square clears that side's.
 // Wave-cooperative and wave-uniform: every lane derives the same scalars from the LDS board, the piece
 // lists are edited one entry per lane, lane 0 writes the scalars.  All lanes must call.
-// INSTANCE: 0 the one-leaf kernels, 1 (LEAF_PARALLEL) the leaf-parallel selection, 2 k_tree_advance -- separate
+// INSTANCE: 0 the one-leaf kernels, 1 the leaf-parallel selection, 2 k_tree_advance, 3 k_play_ply -- separate
 // instances, so that the one-leaf kernels' callees -- and with them the compiler's inlining decisions and the kernels'
 // ISA -- stay exactly what they were before leaf-parallel search and subtree reuse
 template <int INSTANCE = 0>
@@ -718,8 +720,8 @@ __device__ inline void walk_castle(const fpc_board *b, const DevCfg &c, int from
 //              s->nlegal, and apply the reordering of its full make/undo loop.  Skipped when
 //              do_result found a terminal position (ChooseLeaf returns before the mask is built).
 // `player` < 0 -> side to move.  All lanes of the wave must call this (uniform control flow).
-// LEAF_PARALLEL: see make_move_wave
-template <bool LEAF_PARALLEL = false>
+// INSTANCE: see make_move_wave (0 the one-leaf kernels and k_board_ops, 1 the leaf-parallel selection, 3 k_play_ply)
+template <int INSTANCE = 0>
 __device__ inline void wave_position_ops(WaveLds *s, const DevCfg &c, bool do_result, bool do_legal, int player) {
   const int lane = lane_id();
   fpc_board *b = &s->b;
@@ -1230,6 +1232,82 @@ __global__ void __launch_bounds__(256) k_tuples_set_z(fpc_tuple *recs, int count
   const int game = recs[i].game;
   for (int k = 0; k < n; ++k)
     if (game_id[k] == game) { recs[i].z = (recs[i].turn & 1) ? z1[k] : z0[k]; return; }
+}
+
+// ================================================================================================
+// k_play_ply (fpc_search_play, opt-in; the numeric spec is in include/fpc_engine.h and DESIGN 5.4): one wave per game
+// of a FINISHED search picks the move to play from the root's children, makes it on a copy of the root state (board
+// slot 0) and runs GetGameResult for the side to move -- k_board_ops' OP_TAKE then OP_RESULT on that state.  Reads the
+// tree and writes nothing into it.
+//   argmax == 0: weight of child k = powtab[N_k] (pow(N, 1/temperature), tabulated by the host libm); all lanes fetch
+//                the weights into LDS in passes of 64, then ONE lane adds them strictly left to right in f64 -- the
+//                order is the spec (a wave scan rounds differently off temperature 1) -- takes x = uniform * S and
+//                walks the same sums again to the first c_k > x (the last child if there is none);
+//   argmax != 0: the first child with the largest N.
+// A game with a search error or a childless root gets flat = result = -1 and its root state.  A move that cannot be made
+// sets ERR_MOVE in err[] (the call's own array, not t.err) and skips GetGameResult.
+// ================================================================================================
+__global__ void __launch_bounds__(64) k_play_ply(DevCfg c, Tree t, int G, const double *powtab, int powtab_n, int argmax,
+                                                 const double *uniform, int *flat, int *result, fpc_board *next, int *err) {
+  __shared__ WaveLds s;
+  __shared__ double wt[FPC_MAX_MOVES];
+  const int g = blockIdx.x;
+  if (g >= G) return;
+  const int lane = lane_id();
+  const size_t nb = (size_t)g * t.node_cap;
+  const int c0 = t.child0[nb], gerr = t.err[g];
+  int nc = c0 < 0 ? 0 : (int)t.nch[nb];
+  if (nc > FPC_MAX_MOVES) nc = FPC_MAX_MOVES;
+  const double u = uniform[g];
+  lds_load_board(&s, &t.boards[(size_t)g * t.board_cap]);
+  if (gerr != 0 || nc == 0) {
+    lds_store_board(&s, &next[g]);
+    if (lane == 0) { flat[g] = -1; result[g] = -1; err[g] = 0; }
+    return;
+  }
+  for (int base = 0; base < nc; base += 64) {
+    const int k = base + lane;
+    if (k < nc) {
+      const int n = t.N[nb + c0 + k];
+      // a visit count is at most 1 + max_sims and the table holds max_sims + 16 entries: the clamp only keeps a
+      // corrupted count from reading outside it
+      wt[k] = argmax ? (double)n : powtab[n < 0 ? 0 : n < powtab_n ? n : powtab_n - 1];
+    }
+  }
+  __syncthreads();
+  if (lane == 0) {
+    int pick = 0;
+    if (argmax) {
+      double best = wt[0];
+      for (int k = 1; k < nc; ++k)
+        if (wt[k] > best) { best = wt[k]; pick = k; }
+    } else {
+      double S = 0.0;
+      for (int k = 0; k < nc; ++k) S = S + wt[k];
+      const double x = u * S;
+      double ck = 0.0;
+      pick = nc - 1;
+      for (int k = 0; k < nc; ++k) {
+        ck = ck + wt[k];
+        if (ck > x) { pick = k; break; }
+      }
+    }
+    s.first_legal = (int)t.mv[nb + c0 + pick];     // broadcast through LDS
+  }
+  __syncthreads();
+  const int fl = s.first_legal;
+  __syncthreads();
+  int from;
+  const int to = flat_to(c, fl, &from);
+  int e = make_move_wave<3>(&s.b, from, to, c) ? 0 : ERR_MOVE;
+  int res = -1;
+  if (!e) {
+    wave_position_ops<3>(&s, c, true, false, -1);
+    e = s.errbits;
+    res = s.result;
+  }
+  lds_store_board(&s, &next[g]);
+  if (lane == 0) { flat[g] = fl; result[g] = res; err[g] = e; }
 }
 
 // ================================================================================================

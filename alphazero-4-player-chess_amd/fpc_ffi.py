@@ -123,6 +123,8 @@ _SIGS = {
     "fpc_search_results": (C.c_int, [C.c_void_p, P(Board), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
                                      C.c_void_p, C.c_void_p, C.c_void_p]),
     "fpc_search_advance": (C.c_int, [C.c_void_p, P(C.c_int), P(C.c_int), C.c_int, P(Board), P(C.c_int)]),
+    "fpc_search_play": (C.c_int, [C.c_void_p, C.c_double, P(C.c_double), P(C.c_int), P(C.c_int), P(Board)]),
+    "fpc_search_play_ms": (C.c_int, [C.c_void_p, P(C.c_float)]),
     "fpc_search_grandchildren": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, P(C.c_int), C.c_void_p, C.c_void_p]),
     "fpc_load_weights": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
     "fpc_nn_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
@@ -395,6 +397,33 @@ class Engine:
             for g, b in enumerate(roots):
                 C.memmove(C.byref(b), pods[g].ctypes.data, BOARD_BYTES)
         return kept
+
+    def search_finish(self):
+        """fpc_search_results with every array NULL: waits for the search, reads the games' error words (raises on one)
+        and nothing else.  For callers that go on with search_play / search_advance and need no child arrays."""
+        self._chk(self.L.fpc_search_results(self.h, None, None, None, None, 0, None, None, None, None))
+
+    def search_play(self, temperature, uniforms, want_boards=True):
+        """device-side move choice (include/fpc_engine.h fpc_search_play) on the finished search: per game, draw the move
+        from the root's visit counts with uniforms[g] in [0, 1) (temperature 0: first maximum), make it on the root state
+        and run GetGameResult.  Returns (flats int32 [G], results int32 [G], boards): boards is the [G, 288] uint8 array
+        of next states search_begin_np takes (None unless want_boards).  A game with a childless root gets -1, -1 and
+        its root state.  The tree is left as it is: search_advance(flats) or a new search may follow."""
+        G = self.G
+        u = np.ascontiguousarray(uniforms, np.float64)
+        assert u.shape == (G,), (u.shape, G)
+        flats, results = np.zeros(G, np.int32), np.zeros(G, np.int32)
+        pods = np.zeros((G, BOARD_BYTES), np.uint8) if want_boards else None
+        self._chk(self.L.fpc_search_play(self.h, float(temperature), C.cast(u.ctypes.data, P(C.c_double)),
+                                         C.cast(flats.ctypes.data, P(C.c_int)), C.cast(results.ctypes.data, P(C.c_int)),
+                                         _bp(pods) if want_boards and G else None))
+        return flats, results, pods
+
+    def search_play_ms(self):
+        """HIP-event time of k_play_ply in the last search_play (set_timing(True) first)"""
+        ms = C.c_float()
+        self._chk(self.L.fpc_search_play_ms(self.h, C.byref(ms)))
+        return ms.value
 
     # ---- the same position ops on [n, 288] uint8 arrays of PODs (callers that keep a whole batch in one array:
     #      bench.py's per-ply host section, mcts.py's root-children prefetch) ----

@@ -16,6 +16,8 @@ Semantics kept from the reference:
 Returned tuples are compact: (root position POD, flat[], visits[], z); dense tensors are rebuilt with
 tuples.dense_pi / engine.encode when the trainer needs them.
 """
+import math
+
 import numpy as np
 
 import fpc_ffi
@@ -32,6 +34,35 @@ def sample_action(flats, visits, temperature, u):
     return int(flats[min(k, len(flats) - 1)])
 
 
+def sample_move(flats, visits, temperature, u):
+    """The draw of the device path (include/fpc_engine.h fpc_search_play) in plain Python -- the readable
+    statement of that spec and the model the tests hold k_play_ply against.  Children in the tree's order:
+      temperature > 0:  w_k = pow(N_k, 1 / temperature) (libm, f64); c_k = c_{k-1} + w_k strictly left to right;
+                        x = u * S with S the last sum; the pick is the first k with c_k > x, else the last child;
+      temperature == 0: the first child with the largest N.
+    Differs from sample_action only in rounding (f64 sums of unnormalised weights against f32 probabilities
+    renormalised twice): the two pick the same child unless u * S lies within about 1e-5 * S of a c_k."""
+    n = len(flats)
+    if temperature == 0:
+        best = 0
+        for k in range(1, n):
+            if int(visits[k]) > int(visits[best]):
+                best = k
+        return int(flats[best])
+    inv = 1.0 / float(temperature)
+    w = [math.pow(float(int(v)), inv) for v in visits]
+    total = 0.0
+    for x in w:
+        total = total + x
+    x = float(u) * total
+    c = 0.0
+    for k in range(n):
+        c = c + w[k]
+        if c > x:
+            return int(flats[k])
+    return int(flats[n - 1])
+
+
 class Episode:
     def __init__(self, gid):
         self.gid = gid
@@ -42,7 +73,7 @@ class Episode:
         self.length = 0
 
 
-def play(search_fn, eng, start_boards, args, uniforms, continue_fn=None, on_searched=None):
+def play(search_fn, eng, start_boards, args, uniforms, continue_fn=None, on_searched=None, device_play=False):
     """search_fn(list_of_PODs) -> search_results dict (fpc_ffi.Engine.search_results layout) and
     leaves the PODs with the piece-list order the search produced.  uniforms[ply][gid] in [0,1).
     continue_fn (opt-in subtree reuse, not reference semantics; None: every ply is search_fn, as in the reference):
@@ -52,6 +83,10 @@ def play(search_fn, eng, start_boards, args, uniforms, continue_fn=None, on_sear
     PODs and returns the same dict.  Terminal detection stays here, on this loop's own copies of the states.
     on_searched (optional): called as on_searched(ids, ply) right after each ply's search has returned, ids = the game
     ids of that search in batch order (AlphaZero's device replay collects the ply's tuples on the device there).
+    device_play (opt-in, default False): the ply's moves are chosen, made and judged on the device by ONE
+    eng.search_play(temperature, uniforms of the ply) on the search search_fn / continue_fn left finished, instead of
+    the per-game sample_action loop, eng.take_action and eng.game_result.  The draw is sample_move's (the same child
+    as sample_action's except within rounding of a boundary); everything else in this loop is as it is.
     Returns the list of finished Episodes (all games, in game-id order)."""
     R = eng.R
     states = [fpc_ffi.clone_board(b) for b in start_boards]
@@ -69,9 +104,17 @@ def play(search_fn, eng, start_boards, args, uniforms, continue_fn=None, on_sear
             n = int(res["n_children"][i])
             flats, visits = res["flat"][i, :n].copy(), res["visits"][i, :n].copy()
             eps[ids[i]].entries.append((fpc_ffi.clone_board(states[i]), flats, visits))
-            picks.append(sample_action(flats, visits, T, uniforms[ply][ids[i]]))
-        nxt = eng.take_action(states, picks)
-        results = eng.game_result(nxt)
+            if not device_play:
+                picks.append(sample_action(flats, visits, T, uniforms[ply][ids[i]]))
+        if device_play:
+            fl, results, pods = eng.search_play(T, [uniforms[ply][g] for g in ids])
+            if int(fl.min()) < 0:
+                raise RuntimeError("device_play: game %d has no move to play" % ids[int(fl.argmin())])
+            picks = [int(f) for f in fl]
+            nxt = [fpc_ffi.board_of(pods[i]) for i in range(len(states))]
+        else:
+            nxt = eng.take_action(states, picks)
+            results = eng.game_result(nxt)
         keep_s, keep_i, keep_pos, keep_picks = [], [], [], []
         for i in range(len(states)):
             e = eps[ids[i]]

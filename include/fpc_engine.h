@@ -211,6 +211,39 @@ int fpc_search_set_leaves(fpc_engine *e, int leaves, double virtual_loss);
 int fpc_search_advance(fpc_engine *e, const int *src_game /* nullable: 0..n_games-1 */, const int *flat,
                        int n_games, fpc_board *roots_out /* nullable */, int *kept_visits /* nullable */);
 
+/* ---- device-side move choice (opt-in): what a self-play ply does between the finished search and fpc_search_advance /
+ * the next fpc_search_begin -- choose each game's move from the root's visit counts (alphazero.py:104-118), make it
+ * (TakeAction, :119) and judge the game (GetGameResult, :120-123) -- as ONE launch (k_play_ply, one wave per game); the
+ * host sees two ints per game.  Needs a FINISHED search, exactly as fpc_search_advance does (fpc_search_results has been
+ * read -- with every array NULL it reads the error words and nothing else; otherwise FPC_ESTATE).  Reads the tree and
+ * writes nothing into it (no N, W, P, pooled board, alive, err or sims_done changes): the same call with the same
+ * arguments returns the same outputs, and fpc_collect_tuples, fpc_search_advance and fpc_search_begin may follow in any
+ * order.
+ * THE DRAW, per game g with children k = 0..nc-1 in the tree's child order (the order fpc_search_results reports):
+ *   temperature > 0:  w_k = powtab[N_k], powtab[v] = pow((double)v, 1.0 / temperature) for v = 0..max_sims+15, computed by
+ *                     the HOST libm (as the PUCT log table is) and uploaded when the temperature differs from the cached
+ *                     one; the device evaluates no transcendental.  c_k = c_{k-1} + w_k in f64, strictly left to right
+ *                     (one lane walks the at most 256 adds; no wave scan, which would round differently off temperature
+ *                     1); S = c_{nc-1}; x = uniform[g] * S (one f64 multiply); the pick is the first k with c_k > x, or
+ *                     nc-1 if there is none.  At temperature 1 every term is an integer and the arithmetic is exact.
+ *   temperature == 0: the first child with the largest N (arena.py's rule).
+ * THE MOVE: next = the root state (board slot 0) copied, the move made, GetGameResult run for the side to move, under
+ * the engine's current rule set: flat_out, result_out and next_out are bit for bit what fpc_search_results(roots_out) ->
+ * fpc_boards_take_action(roots, flat) -> fpc_boards_game_result(next, NULL) give for the picked moves, the piece-list
+ * order GetGameResult leaves behind included.
+ * A game that carries a search error or has a childless root (a root that is terminal, or that a failed
+ * fpc_search_advance left behind) gets flat_out = -1, result_out = -1 and next_out = its root state.  A game whose
+ * root merely left the search early because a simulation reached a terminal leaf (Q5) has children and is played like
+ * any other, as the host loop plays it.  A move that cannot be made is reported as fpc_boards_take_action reports it
+ * (FPC_EMOVE, "game i: piece missing for move") after the other games are done; it is tracked in an array of the call's
+ * own, never in the search's error words.
+ * FPC_EINVAL (nothing is uploaded or launched): uniform, flat_out or result_out NULL; a uniform that is NaN or outside
+ * [0, 1); a temperature that is negative, NaN or infinite, or for which pow(max_sims + 15, 1 / temperature) is not
+ * finite (use 0 for argmax). */
+int fpc_search_play(fpc_engine *e, double temperature, const double *uniform /* host [G] */,
+                    int *flat_out /* host [G] */, int *result_out /* host [G] */,
+                    fpc_board *next_out /* host [G], nullable */);
+
 /* Root read-back == what alphazero.py:104-110 reads through Node.GetChildren /
  * GetMoveMade().GetFlatIndex() / GetVisitCount().  Arrays are [n_games][max_children].
  * roots_out (nullable): the root states with the piece-list order the search left them in. */
@@ -325,6 +358,8 @@ const char *fpc_nn_kernel(fpc_engine *e);        /* name of the kernel that runs
                                                   * skeleton on the compact image), "k_tower" (developer knobs), "k_conv3x3" (per layer), "" before fpc_load_weights */
 /* HIP-event time of k_replay_decode alone in the last fpc_replay_batch that ran with fpc_set_timing on (else FPC_ESTATE) */
 int fpc_replay_decode_ms(fpc_engine *e, float *ms_out);
+/* the same for k_play_ply in the last fpc_search_play */
+int fpc_search_play_ms(fpc_engine *e, float *ms_out);
 void *fpc_stream(fpc_engine *e);                 /* hipStream_t the engine launches on */
 int fpc_memory_is_host(void);                    /* 1 in the wavefront-emulator build of these sources, where every "device" pointer
                                                   * (enc_dev, logits_dev, the fpc_replay_batch outputs, ...) is host memory; 0 in the product */
