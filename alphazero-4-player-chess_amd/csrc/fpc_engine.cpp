@@ -7,6 +7,7 @@
 // emulator (-DFPC_EMUL, tests/emul/) for the CPU test-suite; that build has no NN and is never
 // loaded by the product modules.
 #include "fpc_tree_kernels.h"
+#include "fpc_pack.h"
 
 #include <algorithm>
 #include <cmath>
@@ -106,6 +107,11 @@ struct fpc_engine {
   size_t rp_idx_cap = 0;
   hipEvent_t rp_ev[2] = {nullptr, nullptr};   // around k_replay_decode while fpc_set_timing is on
   float rp_decode_ms = -1.f;
+  // ---- device-side weight pack (fpc_weights_pack / fpc_load_weights_device)
+  unsigned char *d_pack_tab = nullptr;   // k_pack_conv's descriptor table [pack_tab_convs] + one float (the value bias on its way to the host)
+  int pack_tab_convs = 0;
+  hipEvent_t pk_ev[2] = {nullptr, nullptr};   // around the pack kernels while fpc_set_timing is on
+  float pack_ms = -1.f;
   // ---- stats
   bool timing = false;
   int policy_mode = 0;            // FPC_POLICY_FULL / FPC_POLICY_LEGAL (fpc_search_run only)
@@ -376,6 +382,8 @@ int fpc_create(const fpc_config *cfg, fpc_engine **out) {
       (r = dalloc(e, &e->d_logtab, (size_t)cfg->max_sims + 16)) ||
       (r = dalloc(e, &e->d_rc_meta, (size_t)Gm * 3)))
     return bail(r);
+  e->pack_tab_convs = 2 * 64 + 3;      // networks of up to 64 residual blocks are packed without an allocation
+  if ((r = dalloc(e, &e->d_pack_tab, (size_t)e->pack_tab_convs * sizeof(PackConv) + 16))) return bail(r);
   {
     // log(sqrt(N_parent)) (node.cpp:53-54) tabulated with the HOST libm so that the device PUCT
     // sees exactly the bits the reference's std::log produces; +,*,/,sqrt are IEEE on both sides.
@@ -404,6 +412,7 @@ void fpc_destroy(fpc_engine *e) {
   for (auto &ev : e->evpool) if (ev) (void)hipEventDestroy(ev);
   for (auto &ev : e->rp_ev) if (ev) (void)hipEventDestroy(ev);
   for (auto &ev : e->play_ev) if (ev) (void)hipEventDestroy(ev);
+  for (auto &ev : e->pk_ev) if (ev) (void)hipEventDestroy(ev);
   if (e->stream) (void)hipStreamDestroy(e->stream);
   delete e;
 }
@@ -1528,5 +1537,187 @@ int fpc_debug_tree_stamps(unsigned long long *out32) {
   return hipMemcpyFromSymbol(out32, HIP_SYMBOL(fpc::g_tree_stamps), 32 * sizeof(unsigned long long)) == hipSuccess ? 0 : FPC_ENODEVICE;
 }
 #endif
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------------
+// device-side weight pack (fpc_pack.h)
+namespace {
+
+int pack_cus() {
+#ifdef FPC_EMUL
+  return 256;
+#else
+  return fpc::NN::device_cus();
+#endif
+}
+
+// the geometry a network of this width and depth packs into on this engine's board: fc_layout 0 chooses as
+// weights.default_fc_layout does; shapes fpc_load_weights refuses are refused with its messages
+int pack_geom_from(fpc_engine *e, int hidden, int nblocks, int fc_layout, PackGeom *g, const char *fn) {
+  if (fc_layout < 0 || fc_layout > 2) return fail(e, FPC_EINVAL, "%s: fc_layout must be 0 (default), 1 (k_fc16) or 2 (k_fcw)", fn);
+  const int A = e->dc.A;
+  g->R = e->dc.R; g->RR = e->dc.RR; g->A = A; g->A_ch = e->dc.A_ch; g->F = hidden; g->nblocks = nblocks; g->dtype = e->cfg.nn_dtype ? 1 : 0;
+  g->Fp = (hidden + 127) / 128 * 128;
+  g->Kp = (A + 511) / 512 * 512;
+  if (fc_layout == 0) fc_layout = pk_plan_fcw((A + PK_FCW_COLS - 1) / PK_FCW_COLS * PK_FCW_COLS, g->Kp, pack_cus()) ? 2 : 1;
+  g->fc_layout = fc_layout;
+  const int gw = fc_layout == 2 ? PK_FCW_COLS : 256;
+  g->Np = (A + gw - 1) / gw * gw;
+  return pk_check_geom(g->F, g->nblocks, g->Np, g->Kp, g->fc_layout, A, pack_cus(), &g->fcw_split, &e->err);
+}
+
+// convolution i of the descriptor in blob order: stem, c1[0], c2[0], ..., policy, value
+const fpc_conv_src &conv_at(const fpc_net_src *s, int i) {
+  if (i == 0) return s->stem;
+  if (i <= 2 * s->nblocks) return (i - 1) & 1 ? s->c2[(i - 1) / 2] : s->c1[(i - 1) / 2];
+  return i == 2 * s->nblocks + 1 ? s->pconv : s->vconv;
+}
+
+// argument checks and the geometry of the packed network; nothing is launched
+int pack_geom(fpc_engine *e, const fpc_net_src *s, int fc_layout, PackGeom *g, const char *fn) {
+  if (!s) return fail(e, FPC_EINVAL, "%s: null descriptor", fn);
+  if (e->dc.A_ch > PK_MAXCH || e->dc.A_ch % 8) return fail(e, FPC_EINVAL, "%s: board too large for k_pack_fc's tile", fn);
+  auto conv_ok = [](const fpc_conv_src &c) { return c.w && c.bn_weight && c.bn_bias && c.bn_mean && c.bn_var; };
+  bool ptrs = conv_ok(s->stem) && conv_ok(s->pconv) && conv_ok(s->vconv) && s->fc_w && s->fc_b && s->vfc_w && s->vfc_b;
+  if (s->nblocks > 0 && (!s->c1 || !s->c2)) ptrs = false;
+  for (int i = 0; ptrs && i < s->nblocks; ++i) ptrs = conv_ok(s->c1[i]) && conv_ok(s->c2[i]);
+  if (!ptrs) return fail(e, FPC_EINVAL, "%s: null parameter pointer in the descriptor", fn);
+  const int rc = pack_geom_from(e, s->hidden, s->nblocks, fc_layout, g, fn);
+  if (rc) return rc;
+  for (int i = 0; i < g->nconv(); ++i) {
+    const fpc_conv_src &c = conv_at(s, i);
+    int cin, cout, cin_pad, cout_pad;
+    g->conv_dims(i, &cin, &cout, &cin_pad, &cout_pad);
+    if (c.cin != cin || c.cout != cout)
+      return fail(e, FPC_EINVAL, "%s: convolution %d of the descriptor is %d -> %d channels, this board and hidden width need %d -> %d", fn, i, c.cin, c.cout, cin, cout);
+  }
+  return 0;
+}
+
+// room for the descriptors of `nconv` convolutions (networks of more than 64 blocks: the table grows once)
+int pack_ensure_tab(fpc_engine *e, int nconv) {
+  if (nconv <= e->pack_tab_convs) return 0;
+  unsigned char *grown = nullptr;
+  int r;
+  if ((r = dalloc(e, &grown, (size_t)nconv * sizeof(PackConv) + 16))) return r;
+  (void)hipFree(e->d_pack_tab);
+  e->allocs.erase(std::find(e->allocs.begin(), e->allocs.end(), (void *)e->d_pack_tab));
+  e->d_pack_tab = grown;
+  e->pack_tab_convs = nconv;
+  return 0;
+}
+
+// launches the three pack kernels on the engine's stream (timed if fpc_set_timing is on); the caller synchronises
+int pack_launch(fpc_engine *e, const fpc_net_src *s, const PackGeom &g, const PackDst &d) {
+  const int nconv = g.nconv();
+  if (nconv > e->pack_tab_convs) return fail(e, FPC_ESTATE, "descriptor table too small");
+  std::vector<PackConv> tab((size_t)nconv);
+  int max_items = 0;
+  for (int i = 0; i < nconv; ++i) {
+    const fpc_conv_src &c = conv_at(s, i);
+    PackConv &t = tab[(size_t)i];
+    t.w = c.w; t.b = c.b; t.g = c.bn_weight; t.beta = c.bn_bias; t.mean = c.bn_mean; t.var = c.bn_var; t.eps = c.eps;
+    g.conv_dims(i, &t.cin, &t.cout, &t.cin_pad, &t.cout_pad);
+    t.w16 = d.cw[(size_t)i]; t.b32 = d.cb[(size_t)i];
+    max_items = std::max(max_items, 9 * t.cout_pad * (t.cin_pad / 8));
+  }
+  HIPCHK(e, hipMemcpyAsync(e->d_pack_tab, tab.data(), tab.size() * sizeof(PackConv), hipMemcpyHostToDevice, e->stream));
+  HIPCHK(e, hipStreamSynchronize(e->stream));      // `tab` is pageable host memory about to go out of scope
+  if (e->timing && !e->pk_ev[0]) {
+    HIPCHK(e, hipEventCreate(&e->pk_ev[0]));
+    HIPCHK(e, hipEventCreate(&e->pk_ev[1]));
+  }
+  if (e->timing) HIPCHK(e, hipEventRecord(e->pk_ev[0], e->stream));
+  const int bpc = std::min(64, (max_items + PK_THREADS - 1) / PK_THREADS);
+  FPC_LAUNCH(k_pack_conv, nconv * bpc, PK_THREADS, e->stream, (const PackConv *)e->d_pack_tab, bpc, g.dtype);
+  const int nchunks = (g.RR + PK_PC - 1) / PK_PC;
+  FPC_LAUNCH(k_pack_fc, (g.Np / 16) * nchunks, PK_THREADS, e->stream, s->fc_w, g.A, g.A_ch, g.RR, g.Np, g.Kp, g.dtype, d.fcw);
+  const int mblk = std::min(64, (g.Np + g.RR * 32 + PK_THREADS) / PK_THREADS);
+  FPC_LAUNCH(k_pack_misc, mblk, PK_THREADS, e->stream, s->fc_b, s->vfc_w, s->vfc_b, g.A, g.RR, g.Np, mblk, d.fcb, d.vw, d.vb);
+  HIPCHK(e, hipGetLastError());
+  if (e->timing) HIPCHK(e, hipEventRecord(e->pk_ev[1], e->stream));
+  return 0;
+}
+
+int pack_finish_timing(fpc_engine *e) {
+  e->pack_ms = -1.f;
+  if (e->timing) HIPCHK(e, hipEventElapsedTime(&e->pack_ms, e->pk_ev[0], e->pk_ev[1]));
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fpc_weights_blob_size(const fpc_engine *ce, int hidden, int nblocks, int fc_layout, uint64_t *nbytes) {
+  fpc_engine *e = const_cast<fpc_engine *>(ce);
+  if (!e || !nbytes) return fail(e, FPC_EINVAL, "fpc_weights_blob_size: null argument");
+  USE_DEV(e);
+  PackGeom g;
+  const int rc = pack_geom_from(e, hidden, nblocks, fc_layout, &g, "fpc_weights_blob_size");
+  if (rc) return rc;
+  *nbytes = pk_blob_layout(g, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+  return 0;
+}
+
+int fpc_weights_pack(fpc_engine *e, const fpc_net_src *src, int fc_layout, void *blob_dev, uint64_t cap, uint64_t *nbytes) {
+  if (!e || !blob_dev) return fail(e, FPC_EINVAL, "fpc_weights_pack: null argument");
+  if ((uintptr_t)blob_dev & 15) return fail(e, FPC_EINVAL, "fpc_weights_pack: blob_dev must be 16-byte aligned");
+  USE_DEV(e);
+  PackGeom g;
+  int r;
+  if ((r = pack_geom(e, src, fc_layout, &g, "fpc_weights_pack"))) return r;
+  std::vector<uint64_t> cw, cb;
+  uint64_t fcw, fcb, vw, vb;
+  const uint64_t total = pk_blob_layout(g, &cw, &cb, &fcw, &fcb, &vw, &vb);
+  if (cap < total) return fail(e, FPC_EINVAL, "fpc_weights_pack: the blob needs %llu bytes, cap is %llu", (unsigned long long)total, (unsigned long long)cap);
+  unsigned char *base = (unsigned char *)blob_dev;
+  PackDst d;
+  for (size_t i = 0; i < cw.size(); ++i) { d.cw.push_back((uint16_t *)(base + cw[i])); d.cb.push_back((float *)(base + cb[i])); }
+  d.fcw = (uint16_t *)(base + fcw); d.fcb = (float *)(base + fcb); d.vw = (float *)(base + vw); d.vb = (float *)(base + vb);
+  if ((r = pack_ensure_tab(e, g.nconv()))) return r;      // the last thing that can fail before something is enqueued
+  int32_t hdr[16] = {0, 3, g.R, g.F, g.nblocks, g.dtype, g.A_ch, g.Np, g.Kp, g.fc_layout, 0, 0, 0, 0, 0, 0};
+  memcpy(hdr, "FPCW", 4);
+  HIPCHK(e, hipMemcpyAsync(base, hdr, sizeof(hdr), hipMemcpyHostToDevice, e->stream));
+  if ((r = pack_launch(e, src, g, d))) return r;
+  HIPCHK(e, hipStreamSynchronize(e->stream));
+  if ((r = pack_finish_timing(e))) return r;
+  if (nbytes) *nbytes = total;
+  return 0;
+}
+
+int fpc_load_weights_device(fpc_engine *e, const fpc_net_src *src, int fc_layout) {
+  if (!e) return fail(e, FPC_EINVAL, "fpc_load_weights_device: null engine");
+  USE_DEV(e);
+  PackGeom g;
+  int r;
+  if ((r = pack_geom(e, src, fc_layout, &g, "fpc_load_weights_device"))) return r;
+#ifdef FPC_EMUL
+  return fail(e, FPC_EWEIGHTS, "the internal ResNet exists only in the gfx950 build");
+#else
+  fpc::NN &nn = e->nn;
+  if ((r = pack_ensure_tab(e, g.nconv()))) return r;
+  // same geometry: straight into the live allocations, nothing freed or allocated; else allocate as fpc_load_weights does
+  if (!nn.same_geom(g.F, g.nblocks, g.Np, g.Kp, g.fc_layout) && (r = nn.alloc_net(g.F, g.nblocks, g.Np, g.Kp, g.fc_layout, g.fcw_split, &e->err))) return r;
+  PackDst d;
+  for (fpc::ConvW *cw : nn.convs_in_blob_order()) { d.cw.push_back(cw->w); d.cb.push_back(cw->b); }
+  d.fcw = nn.fcw; d.fcb = nn.fcb; d.vw = nn.vw;
+  d.vb = (float *)(e->d_pack_tab + (size_t)e->pack_tab_convs * sizeof(PackConv));
+  nn.loaded = false;      // the live weights are about to be rewritten: a HIP failure on the way leaves no half-new network in use
+  if ((r = pack_launch(e, src, g, d))) return r;
+  HIPCHK(e, hipMemcpyAsync(&nn.vb, d.vb, 4, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(e, hipStreamSynchronize(e->stream));
+  if ((r = pack_finish_timing(e))) return r;
+  return nn.finish_weights(&e->err);
+#endif
+}
+
+int fpc_weights_pack_ms(fpc_engine *e, float *ms_out) {
+  if (!e || !ms_out) return fail(e, FPC_EINVAL, "bad argument");
+  if (e->pack_ms < 0.f) return fail(e, FPC_ESTATE, "fpc_weights_pack_ms: no weight pack has run with fpc_set_timing on");
+  *ms_out = e->pack_ms;
+  return 0;
+}
 
 }  // extern "C"

@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "fpc_tree_kernels.h"
+#include "fpc_pack.h"
 #include "fpc_tower.h"
 #include "fpc_towerw.h"
 
@@ -491,13 +492,8 @@ struct NN {
   // Blocks are dispatched in id order, one per CU: simulate that and keep the shortest makespan.
   // Layout 2 (k_fcw): every column group of 384 gets the same number of K-splits, chosen so that all blocks run in ONE
   // round (groups x splits <= CUs) with whole stages of 64 per block; plan_fcw() says whether such a split exists.
-  static int plan_fcw(int Np, int Kp, int cus) {
-    const int groups = Np / FCW_COLS, stages = Kp / 64;
-    int best = 0;
-    for (int sk = 1; sk <= 2 * FC_SPLITK && groups * sk <= cus; ++sk)
-      if (stages % sk == 0 && stages / sk >= 4) best = sk;
-    return best;
-  }
+  static int plan_fcw(int Np, int Kp, int cus) { return pk_plan_fcw(Np, Kp, cus); }
+  static_assert(PK_FCW_COLS == FCW_COLS && PK_FCW_MAXSPLIT == 2 * FC_SPLITK, "fpc_pack.h plans k_fcw's split with these");
   void plan_fc() {
     if (fc_layout == 2) { fc_G1 = Np / FCW_COLS; fc_s2 = fc_s1; return; }     // fc_s1 set by load()
     fc_s1 = FC_SPLITK;
@@ -524,49 +520,34 @@ struct NN {
     }
   }
 
-  int load(const void *blob, uint64_t nbytes, std::string *err) {
-    if (nbytes < sizeof(BlobHeader)) { *err = "weight blob too small"; return FPC_EWEIGHTS; }
-    BlobHeader h;
-    memcpy(&h, blob, sizeof(h));
-    if (memcmp(h.magic, "FPCW", 4) || h.version != 3) { *err = "bad weight blob magic/version (this engine reads version 3; version 2 carried the retired 32x32x16 policy-Linear order: export again)"; return FPC_EWEIGHTS; }
-    if (h.R != dc.R || h.A_ch != dc.A_ch) { *err = "weight blob is for a different board size"; return FPC_EWEIGHTS; }
-    if (h.dtype != dtype) { *err = "weight blob dtype differs from engine nn_dtype"; return FPC_EWEIGHTS; }
-    if (h.fc_layout < 1 || h.fc_layout > 2) { *err = "unknown policy-Linear weight layout in weight blob (1 = k_fc16, 2 = k_fcw)"; return FPC_EWEIGHTS; }
-    if (h.F % 64 || h.F < 64 || h.F > 512 || h.nblocks < 0 || h.Np % (h.fc_layout == 2 ? FCW_COLS : 256) || h.Kp % 512 || h.Kp < 1024 || h.Np < dc.A || h.Kp < dc.A) {
-      *err = "unsupported network shape in weight blob (hidden must be a multiple of 64, Np of 256 -- 384 for fc_layout 2 --, Kp of 512)";
-      return FPC_EWEIGHTS;
-    }
-    int fcw_split = 0;
-    if (h.fc_layout == 2) {
-      int cus = 256, dev = 0;
-      hipDeviceProp_t prop;
-      (void)hipGetDevice(&dev);
-      if (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) cus = prop.multiProcessorCount;
-      fcw_split = plan_fcw(h.Np, h.Kp, cus);
-      if (!fcw_split) { *err = "weight blob fc_layout 2 (k_fcw): no one-round K-split for this shape on this device; export with fc_layout 1"; return FPC_EWEIGHTS; }
-    }
+  static int device_cus() {
+    int cus = 256, dev = 0;
+    hipDeviceProp_t prop;
+    (void)hipGetDevice(&dev);
+    if (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) cus = prop.multiProcessorCount;
+    return cus;
+  }
+  // the shapes this engine runs (the host blob's header and the device pack's descriptor are both held to it); *split: k_fcw's K-split
+  int check_geom(int gF, int gnblocks, int gNp, int gKp, int glayout, int *split, std::string *err) const {
+    return pk_check_geom(gF, gnblocks, gNp, gKp, glayout, dc.A, device_cus(), split, err);
+  }
+  bool same_geom(int gF, int gnblocks, int gNp, int gKp, int glayout) const {
+    return loaded && F == gF && nblocks == gnblocks && Np == gNp && Kp == gKp && fc_layout == glayout;
+  }
+  // Frees whatever network was loaded and allocates this one: weights (zeroed), activations, the tower kernels' weight
+  // streams; chooses the kernels.  The weights are then written by load() (upload) or by the device pack, and
+  // finish_weights() derives the tower streams from them.
+  int alloc_net(int gF, int gnblocks, int gNp, int gKp, int glayout, int split, std::string *err) {
     destroy();
-    F = h.F; nblocks = h.nblocks; Np = h.Np; Kp = h.Kp;
-    fc_layout = h.fc_layout;
+    F = gF; nblocks = gnblocks; Np = gNp; Kp = gKp;
+    fc_layout = glayout;
     fc_gw = fc_layout == 2 ? FCW_COLS : 256;
-    if (fc_layout == 2) fc_s1 = fcw_split;
-    const unsigned char *base = (const unsigned char *)blob;
-    uint64_t off = sizeof(BlobHeader);
+    if (fc_layout == 2) fc_s1 = split;
     int rc = 0;
-    auto take = [&](void **dev, uint64_t bytes) -> int {
-      off = (off + 63) & ~63ull;
-      if (off + bytes > nbytes) { *err = "weight blob truncated"; return FPC_EWEIGHTS; }
-      unsigned char *d = nullptr;
-      if ((rc = dmalloc(&d, bytes, err))) return rc;
-      if (hipMemcpy(d, base + off, bytes, hipMemcpyHostToDevice) != hipSuccess) { *err = "weight upload failed"; return FPC_ENODEVICE; }
-      off += bytes;
-      *dev = d;
-      return 0;
-    };
     auto conv = [&](ConvW &cw, int cin, int cout_pad) -> int {
       cw.cin = cin; cw.cout_pad = cout_pad;
-      if ((rc = take((void **)&cw.w, (uint64_t)9 * cout_pad * cin * 2))) return rc;
-      return take((void **)&cw.b, (uint64_t)cout_pad * 4);
+      if ((rc = dmalloc(&cw.w, (size_t)9 * cout_pad * cin, err))) return rc;
+      return dmalloc(&cw.b, (size_t)cout_pad, err);
     };
     const int Fp = (F + GEMM_BN - 1) / GEMM_BN * GEMM_BN;   // Cout rows are zero-padded to the 128-wide tile
     if ((rc = conv(stem, 32, Fp))) return rc;
@@ -574,11 +555,8 @@ struct NN {
     for (int i = 0; i < nblocks; ++i) { if ((rc = conv(c1[i], F, Fp)) || (rc = conv(c2[i], F, Fp))) return rc; }
     if ((rc = conv(pconv, F, 128))) return rc;
     if ((rc = conv(vconv, F, 128))) return rc;
-    if ((rc = take((void **)&fcw, (uint64_t)Np * Kp * 2)) || (rc = take((void **)&fcb, (uint64_t)Np * 4))) return rc;
-    if ((rc = take((void **)&vw, (uint64_t)dc.RR * 32 * 4))) return rc;
-    off = (off + 63) & ~63ull;
-    if (off + 4 > nbytes) { *err = "weight blob truncated"; return FPC_EWEIGHTS; }
-    memcpy(&vb, base + off, 4);
+    if ((rc = dmalloc(&fcw, (size_t)Np * Kp, err)) || (rc = dmalloc(&fcb, (size_t)Np, err))) return rc;
+    if ((rc = dmalloc(&vw, (size_t)dc.RR * 32, err))) return rc;
     // activations
     const size_t rows = (size_t)Mrows + 2 * guard;
     if ((rc = dmalloc(&in16, rows * 32, err))) return rc;
@@ -619,9 +597,29 @@ struct NN {
       // weights in MFMA fragment order [layer][tap][k-step of 32][cout tile of 16][lane][8] (fpc_towerw.h); one slab =
       // one k-step of one tap = F * 64 bytes; TWW_PAD_SLABS slabs of padding behind the last layer (the prefetch runs up
       // to three k-steps ahead without a branch); head convolutions zero-padded to F output channels
-      const int slab = tww_slab(F), ksn = F / 32, tiles = F / 16;
+      const int slab = tww_slab(F), ksn = F / 32;
       if ((rc = dmalloc(&towerW, ((size_t)layers * 9 * ksn + TWW_PAD_SLABS) * slab, err)) || (rc = dmalloc(&stemW, (size_t)9 * slab, err)) ||
           (rc = dmalloc(&towerB, (size_t)layers * 256, err))) return rc;
+    } else if (use_tower) {
+      // k_tower streams every tap as one 32 KiB block already laid out as its LDS image (fpc_tower.h);
+      // layers: c1[0], c2[0], ..., then the value conv and the policy conv
+      if ((rc = dmalloc(&towerW, (size_t)(layers * 9 + 3) * TW_TAP, err)) || (rc = dmalloc(&stemW, (size_t)9 * TW_STEM_TAP, err)) ||
+          (rc = dmalloc(&towerB, (size_t)layers * 256, err))) return rc;
+    }
+    return 0;
+  }
+  // the weight allocations in blob order (fcw, fcb, vw last; the value bias lives on the host)
+  std::vector<ConvW *> convs_in_blob_order() {
+    std::vector<ConvW *> v{&stem};
+    for (int i = 0; i < nblocks; ++i) { v.push_back(&c1[i]); v.push_back(&c2[i]); }
+    v.push_back(&pconv); v.push_back(&vconv);
+    return v;
+  }
+  // after the weight allocations have been (re)written: the tower kernels' weight streams and, if it exists, the
+  // legal-only head's row-major copy are made again in place; waits for the stream
+  int finish_weights(std::string *err) {
+    if (use_towerw) {
+      const int slab = tww_slab(F), ksn = F / 32, tiles = F / 16;
       auto prep = [&](const ConvW &cw, int layer) {
         hipLaunchKernelGGL(k_towerw_prep, dim3((9 * ksn * tiles * 64 + 255) / 256), dim3(256), 0, stream, (const uint16_t *)cw.w,
                            towerW + (size_t)layer * 9 * ksn * slab, 9, cw.cout_pad, F, tiles);
@@ -631,12 +629,7 @@ struct NN {
       prep(vconv, 2 * nblocks);
       prep(pconv, 2 * nblocks + 1);
       hipLaunchKernelGGL(k_towerw_prep, dim3((9 * tiles * 64 + 255) / 256), dim3(256), 0, stream, (const uint16_t *)stem.w, stemW, 9, stem.cout_pad, 32, tiles);
-      if (hipStreamSynchronize(stream) != hipSuccess || hipGetLastError() != hipSuccess) { *err = "k_towerw_prep failed"; return FPC_ENODEVICE; }
     } else if (use_tower) {
-      // k_tower streams every tap as one 32 KiB block already laid out as its LDS image (fpc_tower.h);
-      // layers: c1[0], c2[0], ..., then the value conv and the policy conv
-      if ((rc = dmalloc(&towerW, (size_t)(layers * 9 + 3) * TW_TAP, err)) || (rc = dmalloc(&stemW, (size_t)9 * TW_STEM_TAP, err)) ||
-          (rc = dmalloc(&towerB, (size_t)layers * 256, err))) return rc;
       auto prep = [&](const ConvW &cw, int layer) {
         hipLaunchKernelGGL(k_tower_prep, dim3((9 * 128 * 16 + 255) / 256), dim3(256), 0, stream, (const uint16_t *)cw.w,
                            towerW + (size_t)layer * 9 * TW_TAP, 9, 128);
@@ -646,10 +639,40 @@ struct NN {
       prep(vconv, 2 * nblocks);
       prep(pconv, 2 * nblocks + 1);
       hipLaunchKernelGGL(k_tower_prep, dim3((9 * 128 * 4 + 255) / 256), dim3(256), 0, stream, (const uint16_t *)stem.w, stemW, 9, 32);
-      if (hipStreamSynchronize(stream) != hipSuccess) { *err = "k_tower_prep failed"; return FPC_ENODEVICE; }
     }
+    if (fcw2) launch_unfrag();
+    if (hipStreamSynchronize(stream) != hipSuccess || hipGetLastError() != hipSuccess) { *err = use_towerw ? "k_towerw_prep failed" : use_tower ? "k_tower_prep failed" : "weight load failed"; return FPC_ENODEVICE; }
     loaded = true;
     return 0;
+  }
+
+  int load(const void *blob, uint64_t nbytes, std::string *err) {
+    if (nbytes < sizeof(BlobHeader)) { *err = "weight blob too small"; return FPC_EWEIGHTS; }
+    BlobHeader h;
+    memcpy(&h, blob, sizeof(h));
+    if (memcmp(h.magic, "FPCW", 4) || h.version != 3) { *err = "bad weight blob magic/version (this engine reads version 3; version 2 carried the retired 32x32x16 policy-Linear order: export again)"; return FPC_EWEIGHTS; }
+    if (h.R != dc.R || h.A_ch != dc.A_ch) { *err = "weight blob is for a different board size"; return FPC_EWEIGHTS; }
+    if (h.dtype != dtype) { *err = "weight blob dtype differs from engine nn_dtype"; return FPC_EWEIGHTS; }
+    int fcw_split = 0, rc = 0;
+    if ((rc = check_geom(h.F, h.nblocks, h.Np, h.Kp, h.fc_layout, &fcw_split, err))) return rc;
+    if ((rc = alloc_net(h.F, h.nblocks, h.Np, h.Kp, h.fc_layout, fcw_split, err))) return rc;
+    const unsigned char *base = (const unsigned char *)blob;
+    uint64_t off = sizeof(BlobHeader);
+    auto take = [&](void *dev, uint64_t bytes) -> int {
+      off = (off + 63) & ~63ull;
+      if (off + bytes > nbytes) { *err = "weight blob truncated"; return FPC_EWEIGHTS; }
+      if (hipMemcpy(dev, base + off, bytes, hipMemcpyHostToDevice) != hipSuccess) { *err = "weight upload failed"; return FPC_ENODEVICE; }
+      off += bytes;
+      return 0;
+    };
+    for (ConvW *cw : convs_in_blob_order())
+      if ((rc = take(cw->w, (uint64_t)9 * cw->cout_pad * cw->cin * 2)) || (rc = take(cw->b, (uint64_t)cw->cout_pad * 4))) return rc;
+    if ((rc = take(fcw, (uint64_t)Np * Kp * 2)) || (rc = take(fcb, (uint64_t)Np * 4))) return rc;
+    if ((rc = take(vw, (uint64_t)dc.RR * 32 * 4))) return rc;
+    off = (off + 63) & ~63ull;
+    if (off + 4 > nbytes) { *err = "weight blob truncated"; return FPC_EWEIGHTS; }
+    memcpy(&vb, base + off, 4);
+    return finish_weights(err);
   }
 
   template <int DT, int CINC>
@@ -838,14 +861,17 @@ struct NN {
   }
   // ---- legal-only policy head --------------------------------------------------------------
   // one-time: row-major copy of the policy weights + the legal-logit buffer
+  void launch_unfrag() {
+    const long chunks = (long)Np * (Kp / 8);
+    if (dtype) hipLaunchKernelGGL((k_fc_unfrag<1>), dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, stream, (const uint16_t *)fcw, fcw2, Np, Kp);   // layouts 1 and 2: one fragment order
+    else hipLaunchKernelGGL((k_fc_unfrag<0>), dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, stream, (const uint16_t *)fcw, fcw2, Np, Kp);
+  }
   int ensure_legal_head(std::string *err) {
     if (fcw2) return 0;
     if (Gmax > GEMV_MAXG) { *err = "legal-only policy head supports at most " + std::to_string(GEMV_MAXG) + " games per engine"; return FPC_EINVAL; }
     int rc;
     if ((rc = dmalloc(&fcw2, (size_t)Np * Kp, err)) || (rc = dmalloc(&d_ll, (size_t)Gmax * FPC_MAX_MOVES, err))) return rc;
-    const long chunks = (long)Np * (Kp / 8);
-    if (dtype) hipLaunchKernelGGL((k_fc_unfrag<1>), dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, stream, (const uint16_t *)fcw, fcw2, Np, Kp);   // layouts 1 and 2: one fragment order
-    else hipLaunchKernelGGL((k_fc_unfrag<0>), dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, stream, (const uint16_t *)fcw, fcw2, Np, Kp);
+    launch_unfrag();
     if (hipGetLastError() != hipSuccess) { *err = "k_fc_unfrag launch failed"; return FPC_ENODEVICE; }
     return 0;
   }

@@ -57,6 +57,21 @@ class Tuple(C.Structure):
 assert C.sizeof(Tuple) == 1280
 
 P = C.POINTER
+
+
+class ConvSrc(C.Structure):
+    """fpc_conv_src: one Conv2d(3x3) + BatchNorm2d of the live module, fp32 device pointers (include/fpc_engine.h)."""
+    _fields_ = [("w", P(C.c_float)), ("b", P(C.c_float)), ("bn_weight", P(C.c_float)), ("bn_bias", P(C.c_float)),
+                ("bn_mean", P(C.c_float)), ("bn_var", P(C.c_float)), ("eps", C.c_float), ("cin", C.c_int), ("cout", C.c_int)]
+
+
+class NetSrc(C.Structure):
+    """fpc_net_src: what the device-side weight pack reads (built by weights.net_src)."""
+    _fields_ = [("hidden", C.c_int), ("nblocks", C.c_int), ("stem", ConvSrc), ("pconv", ConvSrc), ("vconv", ConvSrc),
+                ("c1", P(ConvSrc)), ("c2", P(ConvSrc)), ("fc_w", P(C.c_float)), ("fc_b", P(C.c_float)),
+                ("vfc_w", P(C.c_float)), ("vfc_b", P(C.c_float))]
+
+
 BOARD_BYTES = C.sizeof(Board)
 TURN_OFFSET = Board.turn.offset          # byte of a POD row that holds the side to move
 
@@ -128,6 +143,10 @@ _SIGS = {
     "fpc_search_grandchildren": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, P(C.c_int), C.c_void_p, C.c_void_p]),
     "fpc_load_weights": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
     "fpc_nn_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "fpc_weights_blob_size": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, P(C.c_uint64)]),
+    "fpc_weights_pack": (C.c_int, [C.c_void_p, P(NetSrc), C.c_int, C.c_void_p, C.c_uint64, P(C.c_uint64)]),
+    "fpc_load_weights_device": (C.c_int, [C.c_void_p, P(NetSrc), C.c_int]),
+    "fpc_weights_pack_ms": (C.c_int, [C.c_void_p, P(C.c_float)]),
     "fpc_stats_get": (C.c_int, [C.c_void_p, P(Stats)]),
     "fpc_stats_reset": (C.c_int, [C.c_void_p]),
     "fpc_set_timing": (C.c_int, [C.c_void_p, C.c_int]),
@@ -245,6 +264,7 @@ class Engine:
         self.A_ch = self.L.fpc_num_action_channels(board_size)
         self.A = self.L.fpc_action_space_size(board_size)
         self.max_games, self.max_sims = max_games, max_sims
+        self.device = device
         cfg = Config(board_size, invalid_area, max_games, max_sims, avg_children, device, nn_dtype)
         h = C.c_void_p()
         rc = self.L.fpc_create(C.byref(cfg), C.byref(h))
@@ -463,6 +483,55 @@ class Engine:
     def load_weights(self, blob):
         buf = (C.c_char * len(blob)).from_buffer_copy(blob)
         self._chk(self.L.fpc_load_weights(self.h, buf, len(blob)))
+
+    # ---- device-side weight pack (include/fpc_engine.h fpc_weights_pack / fpc_load_weights_device) ----
+    def _net_src(self, model, fc_layout):
+        """(descriptor, keep-alive list, fc_layout word): the module's tensors on this engine's device (the emulator:
+        the host), torch's work on them finished"""
+        import torch
+        import weights
+        dev = "cpu" if self.host_memory else "cuda:%d" % self.device
+        src, keep = weights.net_src(model, dev)
+        if not self.host_memory:
+            torch.cuda.current_stream(self.device).synchronize()
+        if fc_layout is None:
+            fc_layout = weights.FC_LAYOUT if weights.FC_LAYOUT is not None else 0     # 0: the engine chooses as default_fc_layout does
+        return src, keep, int(fc_layout)
+
+    def weights_blob_size(self, hidden, nblocks, fc_layout=0):
+        n = C.c_uint64()
+        self._chk(self.L.fpc_weights_blob_size(self.h, int(hidden), int(nblocks), int(fc_layout), C.byref(n)))
+        return n.value
+
+    def weights_pack(self, model, fc_layout=None):
+        """the module packed ON THE DEVICE into a version-3 blob, read back: the bytes of
+        weights.export_weights(model, nn_dtype, fc_layout) computed op for op in f32 with correctly rounded divide and
+        square root.  Where torch's CPU sqrt is not correctly rounded (0.69 % of random BN variances on the
+        build measured) export_weights itself is one unit off in that channel and the two blobs differ there."""
+        import torch
+        src, keep, fl = self._net_src(model, fc_layout)
+        cap = self.weights_blob_size(src.hidden, src.nblocks, fl)
+        buf = torch.empty(cap + 64, dtype=torch.uint8, device="cpu" if self.host_memory else "cuda:%d" % self.device)
+        ptr = (buf.data_ptr() + 63) & ~63
+        n = C.c_uint64()
+        self._chk(self.L.fpc_weights_pack(self.h, C.byref(src), fl, ptr, cap, C.byref(n)))
+        off = ptr - buf.data_ptr()
+        out = buf[off:off + n.value].cpu().numpy().tobytes()
+        del keep
+        return out
+
+    def load_weights_device(self, model, fc_layout=None):
+        """load_weights(export_weights(model)) without the host: the pack kernels read the module's parameters in device
+        memory and write the engine's weight allocations (in place when the network's geometry has not changed)"""
+        src, keep, fl = self._net_src(model, fc_layout)
+        self._chk(self.L.fpc_load_weights_device(self.h, C.byref(src), fl))
+        del keep
+
+    def weights_pack_ms(self):
+        """HIP-event time of the pack kernels in the last weights_pack / load_weights_device (set_timing(True) first)"""
+        ms = C.c_float()
+        self._chk(self.L.fpc_weights_pack_ms(self.h, C.byref(ms)))
+        return ms.value
 
     def nn_forward(self, enc_ptr, n, logits_ptr, value_ptr):
         self._chk(self.L.fpc_nn_forward(self.h, enc_ptr, n, logits_ptr, value_ptr))

@@ -40,6 +40,12 @@ def _is_resnet(m):
     return isinstance(m, torch.nn.Module) and all(hasattr(m, k) for k in ("startBlock", "backBone", "policyHead", "valueHead"))
 
 
+def _on_engine_device(m, eng):
+    """every parameter and buffer of the module lies on the engine's GPU"""
+    import itertools
+    return all(t.device.type == "cuda" and t.device.index == eng.device for t in itertools.chain(m.parameters(), m.buffers()))
+
+
 class MCTS:
     def __init__(self, gameType, neural_net, args):
         self.gameType = gameType
@@ -62,6 +68,9 @@ class MCTS:
         self._noise_rng = np.random.default_rng(int(args.get("noise_seed", 0))) if self.root_noise else None
         self.leaves = int(args.get("leaves_per_step", 1)) if hasattr(args, "get") else 1
         self.virtual_loss = float(args.get("virtual_loss", 1.0)) if hasattr(args, "get") else 1.0
+        # args["device_weights"] = True (opt-in): a module that lies on the engine's GPU is packed into the engine there
+        # (fpc_load_weights_device: no host copy, in place); any other module takes the host path as before
+        self.device_weights = bool(args.get("device_weights", False)) if hasattr(args, "get") else False
 
     def engine_rows(self, G):
         """rows of the engine handle a search of G games needs (G * leaves_per_step)"""
@@ -72,7 +81,10 @@ class MCTS:
         import weights
         ver = _param_version(self.neural_net)
         if getattr(eng, "weights_version", None) != ver:
-            eng.load_weights(weights.export_weights(self.neural_net, self.nn_dtype))   # the module stays where it is
+            if self.device_weights and _on_engine_device(self.neural_net, eng):
+                eng.load_weights_device(self.neural_net)
+            else:
+                eng.load_weights(weights.export_weights(self.neural_net, self.nn_dtype))   # the module stays where it is
             eng.weights_version = _param_version(self.neural_net)
 
     def add_dirichlet_noise(self, policy, device):

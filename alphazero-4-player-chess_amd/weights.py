@@ -123,3 +123,33 @@ def export_weights(model, dtype=0, fc_layout=None):
         out += b"\0" * ((-len(out)) % 64)
         out += s
     return bytes(out)
+
+
+def net_src(model, device):
+    """The module's parameters as the device-side pack reads them (include/fpc_engine.h fpc_net_src): returns
+    (descriptor, keep).  Every tensor is detach().to(float32).contiguous() on `device` -- no copy for an fp32 module that
+    already lies there -- and `keep` holds them (and the ctypes arrays the descriptor points into) alive: keep it until
+    the call that takes the descriptor has returned.  device "cpu" serves the emulator build, whose "device" memory is
+    host memory."""
+    import fpc_ffi
+    keep = []
+
+    def ptr(t):
+        t = t.detach().to(device=device, dtype=torch.float32).contiguous()
+        keep.append(t)
+        return fpc_ffi.C.cast(t.data_ptr(), fpc_ffi.P(fpc_ffi.C.c_float))
+
+    def conv(cv, bn):
+        return fpc_ffi.ConvSrc(ptr(cv.weight), ptr(cv.bias) if cv.bias is not None else None, ptr(bn.weight), ptr(bn.bias),
+                               ptr(bn.running_mean), ptr(bn.running_var), float(bn.eps), int(cv.weight.shape[1]), int(cv.weight.shape[0]))
+
+    nblocks = len(model.backBone)
+    c1 = (fpc_ffi.ConvSrc * max(nblocks, 1))(*[conv(b.conv1, b.bn1) for b in model.backBone])
+    c2 = (fpc_ffi.ConvSrc * max(nblocks, 1))(*[conv(b.conv2, b.bn2) for b in model.backBone])
+    keep += [c1, c2]
+    fc, vfc = model.policyHead[4], model.valueHead[4]
+    src = fpc_ffi.NetSrc(int(model.startBlock[0].weight.shape[0]), nblocks, conv(model.startBlock[0], model.startBlock[1]),
+                         conv(model.policyHead[0], model.policyHead[1]), conv(model.valueHead[0], model.valueHead[1]),
+                         fpc_ffi.C.cast(c1, fpc_ffi.P(fpc_ffi.ConvSrc)), fpc_ffi.C.cast(c2, fpc_ffi.P(fpc_ffi.ConvSrc)),
+                         ptr(fc.weight), ptr(fc.bias), ptr(vfc.weight), ptr(vfc.bias))
+    return src, keep

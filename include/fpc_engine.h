@@ -260,6 +260,52 @@ int fpc_load_weights(fpc_engine *e, const void *blob, uint64_t nbytes);
 /* forward only: enc_dev [n,24,R,R] f32 -> logits_dev [n,A] f32, value_dev [n] f32 (DEVICE pointers) */
 int fpc_nn_forward(fpc_engine *e, const float *enc_dev, int n, float *logits_dev, float *value_dev);
 
+/* ---- device-side weight pack: the network refreshed from the LIVE torch module, without a host blob ------------------
+ * Hand-written kernels (csrc/fpc_pack.h) read the module's fp32 parameters where they lie in device memory and write the
+ * sections of the version-3 blob -- BN fold (weights._fold op for op in f32), fp32 -> the engine's 16-bit type (round to
+ * nearest even, subnormals kept), the policy Linear's NCHW -> NHWC input permutation, zero padding and MFMA fragment
+ * order -- what weights.export_weights produces, computed op for op in f32 with correctly rounded divide and square root.
+ * (Byte for byte the same blob wherever torch's CPU sqrt is correctly rounded too; on builds where it is one unit off for
+ * some variances -- DESIGN 7.3 -- the HOST blob deviates from this spec in those BatchNorm channels.)  Every pointer of the descriptor is DEVICE memory (host
+ * memory in the emulator build, as with fpc_replay_batch), fp32, contiguous. */
+typedef struct fpc_conv_src {     /* one Conv2d(3x3, padding 1) + BatchNorm2d */
+  const float *w;                 /* [cout][cin][3][3] */
+  const float *b;                 /* [cout], nullable = zeros */
+  const float *bn_weight, *bn_bias, *bn_mean, *bn_var;   /* [cout] each */
+  float eps;                      /* (float)bn.eps: torch adds it in f32 */
+  int cin, cout;
+} fpc_conv_src;
+typedef struct fpc_net_src {
+  int hidden, nblocks;
+  fpc_conv_src stem, pconv, vconv;
+  const fpc_conv_src *c1, *c2;    /* HOST arrays [nblocks] of descriptors */
+  const float *fc_w, *fc_b;       /* policy Linear [A][A] (input index ch*RR+pos, torch's NCHW flatten), [A] */
+  const float *vfc_w, *vfc_b;     /* value Linear [24*RR], [1] */
+} fpc_net_src;
+/* fc_layout: 1 or 2 as in the blob header; 0 = what weights.default_fc_layout(R) chooses (2 where k_fcw has a one-round
+ * K-split on this device, else 1).  The dtype is the engine's nn_dtype.
+ * All three calls launch on the engine's stream, which is synchronised before they return; the caller must have finished
+ * whatever wrote the parameters (the Python binding synchronises torch's current stream first).
+ * Errors -- nothing is launched, and the loaded network stays as it was and stays usable:
+ *   FPC_EINVAL    NULL engine, descriptor or required pointer; cin / cout that do not fit the engine's board (stem 24 ->
+ *                 hidden, blocks hidden -> hidden, policy conv hidden -> A_ch, value conv hidden -> 24); cap too small;
+ *                 blob_dev not 16-byte aligned; fc_layout outside 0..2;
+ *   FPC_EWEIGHTS  a shape fpc_load_weights would refuse (hidden not a multiple of 64 or outside 64..512, layout 2 without
+ *                 a one-round split), with its messages. */
+/* size of the blob such a network packs into */
+int fpc_weights_blob_size(const fpc_engine *e, int hidden, int nblocks, int fc_layout, uint64_t *nbytes);
+/* header + sections (64-byte aligned, order and padding of csrc/fpc_nn.h's blob comment) into blob_dev[0..cap); exists in
+ * the emulator build too.  nbytes (nullable): the blob's size. */
+int fpc_weights_pack(fpc_engine *e, const fpc_net_src *src, int fc_layout, void *blob_dev, uint64_t cap, uint64_t *nbytes);
+/* fpc_load_weights without a host blob.  Same geometry as the loaded network (hidden, nblocks, Np, Kp, fc_layout): packs
+ * straight into the live weight allocations, re-derives the tower kernels' weight streams and the legal-only head's
+ * row-major copy in place and reads the value bias back (4 bytes) -- no hipFree, no hipMalloc.  First load or another
+ * geometry: allocates exactly as fpc_load_weights does, then packs.  Emulator build: FPC_EWEIGHTS, as fpc_load_weights. */
+int fpc_load_weights_device(fpc_engine *e, const fpc_net_src *src, int fc_layout);
+/* HIP-event time of the pack kernels of the last fpc_weights_pack / fpc_load_weights_device made with fpc_set_timing on
+ * (else FPC_ESTATE) */
+int fpc_weights_pack_ms(fpc_engine *e, float *ms_out);
+
 /* ---- training tuples and their episode-end exchange ---------------------------------------
  * The reference keeps (state, pi, z) tuples as Python objects: Board::AppendToMemory(MemoryEntry(state,
  * action_probs)) per ply (alphazero.py:104-112), rewards assigned when the game ends
