@@ -773,6 +773,32 @@ int orc_policy_priors(const float *logits, int R, int turn0, const int *legal_fl
   return 0;
 }
 
+// The legal-only policy head (k_policy_gemv + k_expand_legal).  Numeric spec ("the legal-only
+// head's prior arithmetic"): l_j = the logit of legal move j (ascending flat order) at its rotated source index;
+//   m = max_j l_j;  p_j = fpc_expf(l_j - m), 0 when every l_j is -inf;  T = sequential ascending sum of p_j;
+//   policy error on a NaN among the l_j or not T > 0;  priors = p_j / T.  No other logit of the row is read.
+int orc_policy_priors_legal(const float *logits, int R, int turn0, const int *legal_flat, int n_legal, float *priors) {
+  const int RR = R * R;
+  const float NINF = -std::numeric_limits<float>::infinity();
+  std::vector<float> l(n_legal);
+  bool has_nan = false;
+  float m = NINF;
+  for (int j = 0; j < n_legal; ++j) {
+    const int plane = legal_flat[j] / RR, pos = legal_flat[j] % RR;
+    l[j] = logits[plane * RR + rot90_src(R, -turn0, pos / R, pos % R)];
+    if (l[j] != l[j]) has_nan = true;
+    if (l[j] > m) m = l[j];
+  }
+  float T = 0.f;
+  for (int j = 0; j < n_legal; ++j) {
+    priors[j] = m > NINF ? orc_expf(l[j] - m) : 0.f;
+    T = T + priors[j];
+  }
+  if (has_nan || !(T > 0.f)) return 1;
+  for (int j = 0; j < n_legal; ++j) priors[j] = priors[j] / T;
+  return 0;
+}
+
 // ---- MCTS: node.h:70-78, node.cpp, mcts.py ----
 namespace {
 struct ONode {

@@ -102,6 +102,11 @@ float orc_expf(float x);
  * 0 ok, 1 if the legal mass is 0/NaN (reference would expand every index and throw). */
 int  orc_policy_priors(const float *logits, int R, int turn0, const int *legal_flat, int n_legal,
                        float *priors);
+/* the legal-only policy head (fpc_set_policy_mode(FPC_POLICY_LEGAL)): the same row and the same
+ * arguments, but only the legal moves' logits are read -- m = their maximum, p_j = orc_expf(l_j - m) (0 when every
+ * legal logit is -inf), T = sequential ascending sum, priors p_j / T.  returns 1 on a NaN among them or not T > 0. */
+int  orc_policy_priors_legal(const float *logits, int R, int turn0, const int *legal_flat, int n_legal,
+                             float *priors);
 
 /* ---- MCTS.search (mcts.py:17-43 + node.cpp) ---- */
 typedef struct orc_search_out {

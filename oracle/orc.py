@@ -58,6 +58,7 @@ def lib():
         L.orc_set_root_noise.argtypes = [C.c_void_p, C.c_int, C.c_float]
         L.orc_policy_priors.argtypes = [C.POINTER(C.c_float), C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int,
                                         C.POINTER(C.c_float)]
+        L.orc_policy_priors_legal.argtypes = L.orc_policy_priors.argtypes
         _lib = L
     return _lib
 

@@ -7,7 +7,9 @@ selected is made with orc.take_action and nothing else, an already expanded new 
 the one-ply form: fresh trees, one Model.search.
 
 Board work goes through the oracle's primitives (orc.legal_moves / game_result / take_action / encode) and the priors
-through orc_policy_priors, so that the model and the kernels meet at bit level.  Selection arithmetic is fp64 without
+through orc_policy_priors -- with policy_head="legal" through orc_policy_priors_legal, the arithmetic of the opt-in
+legal-only head (fpc_set_policy_mode) and the ONLY thing the switch changes -- so that the model and the
+kernels meet at bit level.  Selection arithmetic is fp64 without
 contraction (Python floats), the log table is math.log(math.sqrt(n)) as the host table is; f32 work (values, root
 noise) is done on numpy float32 scalars.
 
@@ -37,13 +39,17 @@ class _Node:
         self.state = state                       # made from the parent's state the first time the node is reached
 
 
-def _priors(logits_row, R, rot, legal):
+POLICY_HEADS = ("full", "legal")
+
+
+def _priors(logits_row, R, rot, legal, policy_head="full"):
     L = orc.lib()
     lg = np.ascontiguousarray(logits_row, dtype=np.float32)
     lf = np.ascontiguousarray(legal, dtype=np.int32)
     out = np.zeros(max(len(legal), 1), dtype=np.float32)
-    rc = L.orc_policy_priors(lg.ctypes.data_as(C.POINTER(C.c_float)), R, rot, lf.ctypes.data_as(C.POINTER(C.c_int)),
-                             len(legal), out.ctypes.data_as(C.POINTER(C.c_float)))
+    fn = L.orc_policy_priors_legal if policy_head == "legal" else L.orc_policy_priors
+    rc = fn(lg.ctypes.data_as(C.POINTER(C.c_float)), R, rot, lf.ctypes.data_as(C.POINTER(C.c_int)), len(legal),
+            out.ctypes.data_as(C.POINTER(C.c_float)))
     return rc, out[:len(legal)]
 
 
@@ -56,10 +62,15 @@ def schedule(sims, leaves):
 
 
 class Model:
-    def __init__(self, boards, R, INV, Cpuct, evaluator, rules=0, vl=1.0, noise_eps=0.0):
+    def __init__(self, boards, R, INV, Cpuct, evaluator, rules=0, vl=1.0, noise_eps=0.0, policy_head="full"):
         """boards: orc boards (mutated like the engine mutates its roots' piece lists).  evaluator: numpy callable
-        enc[B,24,R,R] -> (logits[B,A], value[B])."""
+        enc[B,24,R,R] -> (logits[B,A], value[B]).  policy_head: "full" | "legal" (the priors' arithmetic, nothing else)."""
+        assert policy_head in POLICY_HEADS
         self.R, self.INV, self.Cpuct, self.ev, self.rules, self.vl = R, INV, float(Cpuct), evaluator, rules, float(vl)
+        self.policy_head = policy_head
+        # per simulation step: {"rows", "dead": the rows without a leaf to expand (terminal leaf, collision, game over),
+        # "pairs": (live row, legal move) pairs, "turns": the live rows' sides to move, "max_legal"}
+        self.steps = []
         self.noise, self.noise_eps = None, noise_eps
         self.roots = [_Node(0.0, -1, None, state=b) for b in boards]
         self.alive = [True] * len(boards)
@@ -150,6 +161,10 @@ class Model:
                     for p in path:
                         p.VL += 1
             live = [r for r in range(nrows) if rows[r] is not None]
+            self.steps.append({"rows": nrows, "dead": [r for r in range(nrows) if rows[r] is None],
+                               "pairs": sum(len(rows[r][3]) for r in live),
+                               "turns": [rows[r][1].state.turn for r in live],
+                               "max_legal": max([len(rows[r][3]) for r in live], default=0)})
             if not live:
                 continue
             # ---- evaluation of rows 0 .. ks*G-1, dead rows all-zero
@@ -169,7 +184,7 @@ class Model:
                     _, nd, path, legal = row
                     r = k * G + g
                     rot = nd.state.turn if rules & RULES_ROTATION else turn0
-                    prc, pri = _priors(logits[r], R, rot, legal)
+                    prc, pri = _priors(logits[r], R, rot, legal, self.policy_head)
                     if prc:
                         return -3
                     if self.noise is not None and nd is self.roots[g]:
@@ -223,13 +238,13 @@ class Model:
         return out
 
 
-def search(boards, R, INV, sims, Cpuct, evaluator, leaves, vl=1.0, rules=0, noise=None, noise_eps=0.0):
+def search(boards, R, INV, sims, Cpuct, evaluator, leaves, vl=1.0, rules=0, noise=None, noise_eps=0.0, policy_head="full"):
     """One ply on fresh trees.  noise: float32 [G][MAX_MOVES] gamma draws or None.
-    Returns (rc of Model.search, Model.results() or None, counts {"collisions", "terminals"})."""
-    model = Model(boards, R, INV, Cpuct, evaluator, rules=rules, vl=vl, noise_eps=noise_eps)
+    Returns (rc of Model.search, Model.results() or None, counts {"collisions", "terminals", "steps": Model.steps})."""
+    model = Model(boards, R, INV, Cpuct, evaluator, rules=rules, vl=vl, noise_eps=noise_eps, policy_head=policy_head)
     model.set_noise(noise)
     rc = model.search(sims, leaves)
-    return rc, model.results() if rc == 0 else None, model.counts
+    return rc, model.results() if rc == 0 else None, dict(model.counts, steps=model.steps)
 
 
 # ---- the engine through the step-wise C-ABI -----------------------------------------------------------------------

@@ -6,18 +6,22 @@ must give the float64 reference's bits.  No tolerance anywhere.  tests/test_towe
 product of these inputs is dead and that faults of the Linear's own decomposition are flagged.
 
 Second half: the same Linear scaled by a power of two makes the internal network's logits reproducible on the CPU, so
-the fused search (fpc_search_run: k_fc_reduce's softmax records, the slab reader logit_at) meets the oracle directly."""
+the fused search (fpc_search_run: k_fc_reduce's softmax records, the slab reader logit_at) meets the oracle directly --
+and the opt-in legal-only head (k_fc_unfrag, k_policy_gemv, k_expand_legal(_select)(_multi)) the search model with
+policy_head="legal" (tests/legal_head_cases.py; tests/test_legal_head_cpu.py proves those cases able to fail)."""
+import time
+
 import numpy as np
 import pytest
 
+import legal_head_cases as lc
 import search_model as sm
 import tower_probe as tp
 from fpc_testlib import make_engine, roots_of
+from legal_head_cases import G, INV_OF, SIMS, search_setup
 from oracle import orc
 
 pytestmark = pytest.mark.gpu
-
-INV_OF = {8: 2, 9: 2, 10: 2, 11: 3, 12: 3, 13: 3, 14: 3}
 
 
 @pytest.mark.parametrize("case", tp.LINEAR_CASES, ids=tp.linear_case_id)
@@ -59,44 +63,14 @@ def test_dense_integer_linear_every_element(case, monkeypatch):
 # (R, hidden, operand type, layout, s): s is the power of two that brings the reference's largest |logit| over the 12
 # root positions into [8, 16) -- computed from the reference in the test and held against this record
 SEARCH_CASES = [(8, 128, 1, 2, 9), (8, 128, 0, 1, 9), (10, 128, 1, 1, 9), (14, 128, 1, 2, 10), (8, 256, 1, 2, 9)]
-G, SIMS = 12, 48
 
 
-def search_setup(R, hidden, dtype, seed=31):
-    """the network, 12 root positions (seeded random playouts through the oracle), the scale exponent and the evaluator
-    that IS the float64 reference: everything of a search case that needs no GPU"""
-    # 3 blocks for both operand types: positions of real games fill 1 % of the input planes (probe_inputs: 25 %), the
-    # activations stay below 2^8 -- held by integer_conditions on every call -- and two blocks leave too few distinct values
-    blocks = 3
-    m = tp.integer_net(R, blocks, hidden, 100 * R + blocks)
-    layers = tp.conv_layers(m, dtype)
-    W, bias = tp.dense_weights(R)
-    boards = sm.positions(R, G, seed=seed + R)
-
-    def logits_of(enc):
-        assert np.isin(enc, (0.0, 1.0)).all()
-        ref = tp.forward(layers, enc, dtype)
-        tp.integer_conditions(ref, dtype)
-        tp.linear_conditions(ref["policy"].reshape(enc.shape[0], -1), W, bias)
-        return tp.expected_logits(ref["policy"], "dense_int", R)
-
-    top = float(np.abs(logits_of(orc.encode(boards, R))).max())
-    s = int(np.floor(np.log2(top))) - 3
-    assert 8.0 <= top * 2.0 ** -s < 16.0
-
-    def ev(enc):
-        lg = logits_of(np.asarray(enc, np.float64)) * 2.0 ** -s
-        return lg.astype(np.float32), np.zeros(enc.shape[0], np.float32)
-
-    return m, boards, s, ev
-
-
-def _engine_for_search(R, hidden, dtype, layout, m, boards, s, rows):
+def _engine_for_search(R, hidden, dtype, layout, m, boards, s, rows, max_sims=SIMS):
     import torch
-    eng = make_engine("gpu", R, INV_OF[R], max_games=rows, max_sims=SIMS, nn_dtype=dtype)
+    eng = make_engine("gpu", R, INV_OF[R], max_games=rows, max_sims=max_sims, nn_dtype=dtype)
     eng.load_weights(tp.splice(m, tp.tail(R, dtype, layout, "dense_scaled", s=s)))
     # the value Linear is all zero: the engine's value is tanh(0), exactly
-    x = torch.from_numpy(orc.encode(boards, R)).cuda()
+    x = torch.from_numpy(orc.encode(boards[:G], R)).cuda()
     lg = torch.full((G, eng.A), float("nan"), device="cuda")
     va = torch.full((G,), float("nan"), device="cuda")
     eng.nn_forward(x.data_ptr(), G, lg.data_ptr(), va.data_ptr())
@@ -147,5 +121,67 @@ def test_fused_leaf_parallel_search_on_the_internal_network_meets_the_model(monk
         res = eng.search_results(roots=roots)
         sm.compare(eng, res, model, ("internal network, 2 leaves", R), grand_every=3)
         eng.set_leaves(1)
+    finally:
+        eng.close()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the legal-only policy head against the search model with the legal head's prior arithmetic
+# ---------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", list(lc.LEGAL_CASES))
+def test_legal_only_head_meets_the_model_bit_for_bit(name, monkeypatch):
+    """fpc_set_policy_mode(FPC_POLICY_LEGAL) + fpc_search_run on the integer network + "dense_scaled" Linear against
+    search_model with policy_head="legal" fed by the float64 reference: every partial sum of a logit is an integer times
+    2^-s below 2^24 (linear_conditions, asserted on every evaluator call), so k_policy_gemv's logits must be the
+    reference's in every bit whatever the order of its v_dot2 accumulators and its butterfly, and the priors are the
+    spec of DESIGN.md 5.  Root N, children, visits, f32 priors, f64 value sums, list orders and, for every third game,
+    the grandchildren: all bits, no tolerance.  The case's coverage conditions are asserted from the model first."""
+    c = lc.LEGAL_CASES[name]
+    R, K = c["R"], c["K"]
+    monkeypatch.delenv("FPC_DEV_KNOBS", raising=False)
+    case = lc.legal_case(name)
+    print(name, lc.check_coverage(name, case), "model: %.1f s of host time" % case["seconds"])
+    boards = case["boards"]
+    t0 = time.time()
+    eng = _engine_for_search(R, c["hidden"], c["dtype"], c["layout"], case["m"], boards, case["s"], len(boards) * K, c["sims"])
+    try:
+        assert (eng.L.fpc_nn_kernel(eng.h) or b"").decode() == ("k_towerc" if R == 14 else "k_towerw")
+        roots = roots_of(boards, R)
+        eng.set_rules(c["rules"])
+        eng.set_policy_mode(True)
+        eng.set_leaves(K)
+        eng.search_begin(roots, 3.0)
+        eng.search_run(c["sims"])
+        res = eng.search_results(roots=roots)
+        sm.compare(eng, res, case["model"], ("legal-only head", name), grand_every=3)
+        eng.set_leaves(1)
+    finally:
+        eng.close()
+    print(name, "engine and comparison: %.1f s" % (time.time() - t0))
+
+
+def test_legal_only_head_refuses_more_than_2048_games(monkeypatch):
+    """GEMV_MAXG: k_policy_gemv's pair offsets live in 2049 ints of LDS.  An engine of 2049 games (max_sims 1: 97 nodes
+    and 3 boards per game) refuses the legal head in fpc_search_run with FPC_EINVAL and goes on with the full head: the
+    same 12 roots then meet the oracle bit for bit."""
+    from engine_cases import _compare_search
+    R, hidden, dtype, layout, s_rec = SEARCH_CASES[0]
+    monkeypatch.delenv("FPC_DEV_KNOBS", raising=False)
+    m, boards, s, ev = search_setup(R, hidden, dtype)
+    assert s == s_rec
+    rc, oref = orc.search([orc.clone(b) for b in boards], R, INV_OF[R], 1, 3.0, ev)
+    assert rc == 0
+    eng = _engine_for_search(R, hidden, dtype, layout, m, boards, s, 2049, max_sims=1)
+    try:
+        eng.set_policy_mode(True)
+        eng.search_begin(roots_of(boards, R), 3.0)
+        assert eng.L.fpc_search_run(eng.h, 1) == -1                  # FPC_EINVAL
+        assert "at most 2048 games" in (eng.L.fpc_last_error(eng.h) or b"").decode()
+        eng.set_policy_mode(False)
+        roots = roots_of(boards, R)
+        eng.search_begin(roots, 3.0)
+        eng.search_run(1)
+        res = eng.search_results(roots=roots)
+        _compare_search(res, oref, ("full head after the refusal", R))
     finally:
         eng.close()
