@@ -21,6 +21,10 @@ device_play (default False) -- each ply's moves are drawn, made and judged on th
 (fpc_ffi.Engine.search_play on the finished search) instead of a per-game numpy draw and two board-op round trips; the
 draw is selfplay.sample_move's: the inverse CDF over pow(visits, 1/temperature) in f64, which picks sample_action's
 child except within rounding of a boundary.  Composes with reuse_tree and device_replay.
+refill (default False) -- learn() plays the num_games of an iteration as ONE run of num_parallel_games slots in which
+a finished game's batch position is taken by a new game (play(total_games=num_games), selfplay.play(refill=...)) instead
+of num_games // num_parallel_games runs that shrink to their longest game; with reuse_tree the rows that go on keep their
+subtrees beside the fresh ones (fpc_search_advance_refill).  Composes with reuse_tree, device_play and device_replay.
 """
 import numpy as np
 import torch
@@ -64,14 +68,18 @@ class AlphaZero:
         reuse = bool(self.args.get("reuse_tree", False)) if hasattr(self.args, "get") else False
         return az.engine(self.mcts.engine_rows(G), int(self.args["num_searches"]) * (2 if reuse else 1), self.mcts.nn_dtype if self.mcts._native else None)
 
-    def play(self):
+    def play(self, total_games=None):
+        """One self-play run of num_parallel_games games; total_games (at least that many): the batch starts with
+        num_parallel_games and every finished game's position is refilled with a new game until total_games have been
+        started (selfplay.play(refill=...)); with reuse_tree the kept rows keep their subtrees beside the fresh ones."""
         G = int(self.args["num_parallel_games"])
-        games = [self._new_game() for _ in range(G)]
+        total = G if total_games is None else max(int(total_games), G)
+        games = [self._new_game() for _ in range(total)]
         reuse = bool(self.args.get("reuse_tree", False)) if hasattr(self.args, "get") else False
         device_play = bool(self.args.get("device_play", False)) if hasattr(self.args, "get") else False
         eng = self._engine()
         L = int(self.args["max_game_length"])
-        uniforms = torch.rand(L, G, generator=self.gen, dtype=torch.float64).tolist()
+        uniforms = torch.rand(L, total, generator=self.gen, dtype=torch.float64).tolist()
 
         def search_fn(pods):
             boards = [self.gameType._wrap(p) for p in pods]
@@ -88,20 +96,21 @@ class AlphaZero:
         def continue_fn(keep_idx, picks, pods):
             return self.mcts.continue_search(pods, keep_idx, picks)
 
-        where = {}                                        # device replay: (game id, ply) -> index of the collected tuple
+        where = {}                                        # device replay: (game id, loop step) -> index of the collected tuple
 
-        def on_searched(ids, ply):
+        def on_searched(ids, step):
             for g in ids:
-                where[(g, ply)] = len(where)
-            eng.collect_tuples(ids, ply)
+                where[(g, step)] = len(where)
+            eng.collect_tuples(ids, step)
 
         if self.device_replay:
             if eng is not self.experience_buffer.eng:
                 raise RuntimeError("device_replay: the engine handle was re-created (alphazero_cpp.engine grew or was "
                                    "reconfigured) and the replay rings went with it")
-            eng.tuples_reserve(L * G)
-        episodes = selfplay.play(search_fn, eng, [g._b for g in games], self.args, uniforms, continue_fn=continue_fn if reuse else None,
-                                 on_searched=on_searched if self.device_replay else None, device_play=device_play)
+            eng.tuples_reserve(L * total)
+        episodes = selfplay.play(search_fn, eng, [g._b for g in games[:G]], self.args, uniforms, continue_fn=continue_fn if reuse else None,
+                                 on_searched=on_searched if self.device_replay else None, device_play=device_play,
+                                 refill=[g._b for g in games[G:]] if total > G else None)
         split = self.args["replay_buffer_capacity"] / (self.args["replay_buffer_capacity"] + self.args["validation_buffer_capacity"])
         if self.device_replay:
             z_team = np.zeros((2, len(episodes)), np.float32)      # z by (game, team of the side to move), as the Episodes have it
@@ -109,9 +118,10 @@ class AlphaZero:
             for k, ep in enumerate(episodes):
                 for ply, ((pod, _, _), z) in enumerate(zip(ep.entries, ep.z)):
                     z_team[pod.turn & 1, k] = z
-                    src.append(where[(ep.gid, ply)])
+                    src.append(where[(ep.gid, ep.start + ply)])
                     ring_of.append(0 if torch.rand(1, generator=self.gen).item() < split else 1)
-            eng.tuples_set_z([ep.gid for ep in episodes], z_team[0], z_team[1])
+            for k in range(0, len(episodes), eng.max_games):      # fpc_tuples_set_z takes max_games games per call
+                eng.tuples_set_z([ep.gid for ep in episodes[k:k + eng.max_games]], z_team[0, k:k + eng.max_games], z_team[1, k:k + eng.max_games])
             eng.replay_push(src_index=src, ring_of=ring_of)
             return episodes
         for ep in episodes:                               # handle_terminal_state, alphazero.py:53-78
@@ -168,8 +178,11 @@ class AlphaZero:
     def learn(self):                                      # alphazero.py:260-277
         for _ in range(int(self.args["num_iterations"])):
             self.model.eval()
-            for _ in range(int(self.args["num_games"]) // int(self.args["num_parallel_games"])):
-                self.play()
+            if bool(self.args.get("refill", False)) if hasattr(self.args, "get") else False:
+                self.play(total_games=int(self.args["num_games"]))     # one full batch, refilled up to num_games
+            else:
+                for _ in range(int(self.args["num_games"]) // int(self.args["num_parallel_games"])):
+                    self.play()
             self.model.train()
             self.train()
             self.model.eval()

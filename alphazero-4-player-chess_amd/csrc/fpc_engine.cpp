@@ -73,6 +73,8 @@ struct fpc_engine {
   Tree t2{};                      // the second set of node arrays + board pool (only those nine members): k_tree_advance writes
                                   // the re-rooted trees there and the host swaps the two sets; allocated on the first advance
   int *d_adv = nullptr;           // [2][max_games] src_game | flat of one advance
+  fpc_board *d_fresh = nullptr;   // [max_games] start boards of the rows fpc_search_advance_refill refills
+  std::vector<fpc_board> fresh_stage;  // their host staging (the entries at kept positions are not read from the caller)
   // ---- device-side move choice (fpc_search_play); allocated on the first call
   double *d_powtab = nullptr;     // [max_sims + 16] pow(v, 1 / powtab_T) by the host libm
   double powtab_T = -1.0;         // temperature the uploaded table was made for (-1: none yet)
@@ -830,15 +832,11 @@ int fpc_search_grandchildren(fpc_engine *e, int game, int child_idx, int max_chi
 // swaps the two sets, reads the kept root visit counts back and counts max(kept) - 1 simulations as issued: a node
 // created with N = 1 and now at N = n has had n - 1 simulations through it, which is the accounting of a fresh root
 // after n - 1 simulations for the log table, the board pool and the node pool, so admit() holds as it is.
-int fpc_search_advance(fpc_engine *e, const int *src_game, const int *flat, int n_games, fpc_board *roots_out, int *kept_visits) {
-  if (!e || !flat) return fail(e, FPC_EINVAL, "bad argument");
-  if (!e->searching || e->stepping) return fail(e, FPC_ESTATE, "fpc_search_advance needs a finished search: fpc_search_results has not been read");
+// fpc_search_advance_refill is the same launch with fresh rows among the kept ones (src_game[i] == -1): a fresh
+// root counts as kept with N = 1, i.e. 0 simulations issued.
+static int advance_impl(fpc_engine *e, const int *src_game, const int *flat, const fpc_board *fresh, int n_games, fpc_board *roots_out,
+                        int *kept_visits) {
   USE_DEV(e);
-  if (n_games < 1) return fail(e, FPC_EINVAL, "n_games must be positive");
-  if (!src_game && n_games > e->G) return fail(e, FPC_EINVAL, "n_games %d > the %d games of the finished search", n_games, e->G);
-  for (int i = 0; src_game && i < n_games; ++i)
-    if (src_game[i] < 0 || src_game[i] >= e->G || (i > 0 && src_game[i] <= src_game[i - 1]))
-      return fail(e, FPC_EINVAL, "src_game must be strictly ascending within 0..%d (entry %d is %d)", e->G - 1, i, src_game[i]);
   int r;
   if ((r = check_rows(e, e->leaves, n_games))) return r;
   if (e->t.noise && e->noise_n != n_games)
@@ -849,15 +847,22 @@ int fpc_search_advance(fpc_engine *e, const int *src_game, const int *flat, int 
       (!u.mv && (r = dalloc(e, &u.mv, nn))) || (!u.parent && (r = dalloc(e, &u.parent, nn))) || (!u.child0 && (r = dalloc(e, &u.child0, nn))) ||
       (!u.nch && (r = dalloc(e, &u.nch, nn))) || (!u.bslot && (r = dalloc(e, &u.bslot, nn))) ||
       (!u.boards && (r = dalloc(e, &u.boards, (size_t)e->cfg.max_games * t.board_cap))) ||
-      (!e->d_adv && (r = dalloc(e, &e->d_adv, (size_t)2 * e->cfg.max_games))))
+      (!e->d_adv && (r = dalloc(e, &e->d_adv, (size_t)2 * e->cfg.max_games))) ||
+      (fresh && !e->d_fresh && (r = dalloc(e, &e->d_fresh, (size_t)e->cfg.max_games))))
     return r;
   int *d_src = e->d_adv, *d_flat = e->d_adv + e->cfg.max_games;
   if (src_game) HIPCHK(e, hipMemcpyAsync(d_src, src_game, (size_t)n_games * sizeof(int), hipMemcpyHostToDevice, e->stream));
   HIPCHK(e, hipMemcpyAsync(d_flat, flat, (size_t)n_games * sizeof(int), hipMemcpyHostToDevice, e->stream));
+  if (fresh) {                      // only the rows that are refilled are read from the caller
+    e->fresh_stage.assign((size_t)n_games, fpc_board{});
+    for (int i = 0; i < n_games; ++i)
+      if (src_game[i] < 0) e->fresh_stage[i] = fresh[i];
+    HIPCHK(e, hipMemcpyAsync(e->d_fresh, e->fresh_stage.data(), (size_t)n_games * sizeof(fpc_board), hipMemcpyHostToDevice, e->stream));
+  }
   Tree o = t;
   o.N = u.N; o.W = u.W; o.P = u.P; o.mv = u.mv; o.parent = u.parent; o.child0 = u.child0; o.nch = u.nch; o.bslot = u.bslot; o.boards = u.boards;
   FPC_LAUNCH(k_tree_advance, n_games, 64, e->stream, e->dc, t, o, n_games, src_game ? (const int *)d_src : (const int *)nullptr,
-             (const int *)d_flat, e->d_VL, e->d_rc_meta, e->d_roots);
+             (const int *)d_flat, fresh ? (const fpc_board *)e->d_fresh : (const fpc_board *)nullptr, e->d_VL, e->d_rc_meta, e->d_roots);
   HIPCHK(e, hipGetLastError());
   std::swap(t.N, u.N); std::swap(t.W, u.W); std::swap(t.P, u.P); std::swap(t.mv, u.mv); std::swap(t.parent, u.parent);
   std::swap(t.child0, u.child0); std::swap(t.nch, u.nch); std::swap(t.bslot, u.bslot); std::swap(t.boards, u.boards);
@@ -874,6 +879,44 @@ int fpc_search_advance(fpc_engine *e, const int *src_game, const int *flat, int 
   e->sims_issued = (long)*std::max_element(kept.begin(), kept.end()) - 1;
   if (kept_visits) std::copy(kept.begin(), kept.end(), kept_visits);
   return err_to_status(e, errs, "game");
+}
+
+int fpc_search_advance(fpc_engine *e, const int *src_game, const int *flat, int n_games, fpc_board *roots_out, int *kept_visits) {
+  if (!e || !flat) return fail(e, FPC_EINVAL, "bad argument");
+  if (!e->searching || e->stepping) return fail(e, FPC_ESTATE, "fpc_search_advance needs a finished search: fpc_search_results has not been read");
+  if (n_games < 1) return fail(e, FPC_EINVAL, "n_games must be positive");
+  if (!src_game && n_games > e->G) return fail(e, FPC_EINVAL, "n_games %d > the %d games of the finished search", n_games, e->G);
+  for (int i = 0; src_game && i < n_games; ++i)
+    if (src_game[i] < 0 || src_game[i] >= e->G || (i > 0 && src_game[i] <= src_game[i - 1]))
+      return fail(e, FPC_EINVAL, "src_game must be strictly ascending within 0..%d (entry %d is %d)", e->G - 1, i, src_game[i]);
+  return advance_impl(e, src_game, flat, nullptr, n_games, roots_out, kept_visits);
+}
+
+int fpc_search_advance_refill(fpc_engine *e, const int *src_game, const int *flat, const fpc_board *fresh, int n_games, fpc_board *roots_out,
+                              int *kept_visits) {
+  if (!e || !flat) return fail(e, FPC_EINVAL, "bad argument");
+  if (!e->searching || e->stepping)
+    return fail(e, FPC_ESTATE, "fpc_search_advance_refill needs a finished search: fpc_search_results has not been read");
+  if (n_games < 1) return fail(e, FPC_EINVAL, "n_games must be positive");
+  if (!src_game && n_games > e->G) return fail(e, FPC_EINVAL, "n_games %d > the %d games of the finished search", n_games, e->G);
+  bool any_fresh = false;
+  for (int i = 0, last = -1; src_game && i < n_games; ++i) {
+    const int sg = src_game[i];
+    if (sg == -1) {
+      if (!fresh) return fail(e, FPC_EINVAL, "src_game[%d] is -1 (a fresh row) and fresh is NULL", i);
+      any_fresh = true;
+      continue;
+    }
+    if (sg < -1 || sg >= e->G || sg <= last)
+      return fail(e, FPC_EINVAL, "src_game must be -1 (a fresh row) or strictly ascending within 0..%d (entry %d is %d)", e->G - 1, i, sg);
+    last = sg;
+  }
+  for (int i = 0; any_fresh && i < n_games; ++i) {
+    int r;
+    if (src_game[i] == -1 && (r = check_boards(e, fresh + i, 1)))
+      return fail(e, FPC_EINVAL, "fresh[%d]: not a board fpc_search_begin takes (castling rights, piece-list length or turn)", i);
+  }
+  return advance_impl(e, src_game, flat, any_fresh ? fresh : nullptr, n_games, roots_out, kept_visits);
 }
 
 // ------------------------------------------------------------------------------------------------

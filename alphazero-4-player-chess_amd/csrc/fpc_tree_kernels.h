@@ -13,7 +13,8 @@
 //   k_expand_select  k_expand of simulation step s + k_select of step s+1 in one launch
 //   k_select_multi / k_expand(_legal)(_select)_multi  the same for the opt-in leaf-parallel search (K leaves per game
 //                    per step, virtual loss; fpc_search_set_leaves): the descent is select_game's, row k*G + g per leaf
-//   k_tree_advance   opt-in subtree reuse (fpc_search_advance): re-roots every game's tree on the move played, out of place
+//   k_tree_advance   opt-in subtree reuse (fpc_search_advance / _refill): re-roots every game's tree on the move played, out of place,
+//                    and starts fresh games in the rows that are refilled
 //   k_play_ply       opt-in device-side move choice (fpc_search_play): draws each game's move from the finished search's root
 //                    visit counts, makes it on the root state and runs GetGameResult on the result
 //   k_replay_store / k_replay_decode  opt-in device-resident replay (fpc_replay_*): training records into ring slots, and any
@@ -2047,10 +2048,19 @@ __global__ void __launch_bounds__(64) k_expand_legal_select_multi(DevCfg c, Tree
 // becomes node 0 (parent -1, move 0xffff, N / W kept), its subtree follows with N, W, P, move, the children's order
 // and every materialised board; the rest of the old tree is dropped.
 //
-// OUT OF PLACE: games move to lower indices and the blocks run concurrently, so block g would overwrite a region that
-// another block is still reading.  `t` is the finished search (read only, apart from the per-game scalars, which no
-// block reads), `o` the same Tree with the eight node arrays and the board pool replaced by the second set; the host
-// swaps the two sets after the launch.
+// OUT OF PLACE: games move to other indices -- lower ones when games are dropped, and, since fpc_search_advance_refill
+// puts fresh rows between the kept ones, higher ones as well -- and the blocks run concurrently, so block g would
+// overwrite a region that another block is still reading.  `t` is the finished search (read only, apart from the
+// per-game scalars, which no block reads), `o` the same Tree with the eight node arrays and the board pool replaced by
+// the second set; the host swaps the two sets after the launch.  Neither direction matters to the scheme: block g reads
+// only region src_game[g] of `t` and writes only region g of `o` and the scalars of game g.
+//
+// FRESH ROWS (fpc_search_advance_refill): src_game[g] == -1 starts a new game in region g on fresh[g], in the state
+// k_search_init leaves a game in (N = 1, W = 0, no children, board slot 0 = fresh[g], one node, one board, alive, no
+// error, no leaf, no pending visit), kept[g] = 1, roots_out[g] = fresh[g]; flat[g] is not read.  A block is one wave
+// and src_game[g] is the same in all of its lanes, so the two kinds of row never meet at a barrier: the fresh kind
+// returns before the first __syncthreads, as a block with g >= G does.  Root noise reaches such a root when it is
+// expanded (n == 0), from row g of the noise.
 //
 // Breadth-first append, one wave per game: new node j keeps its OLD (child0, nch) until it is processed.  64 queue
 // entries at a time: a wave scan of their child counts places every entry's child block at the tail (blocks stay
@@ -2064,17 +2074,35 @@ __global__ void __launch_bounds__(64) k_expand_legal_select_multi(DevCfg c, Tree
 // Root noise: a new root that is already expanded gets it here, child i (ascending flat order) from gamma[g][i], with
 // expand_finish's operations in expand_finish's order; an unexpanded one gets it when it is expanded (n == 0).
 // ================================================================================================
-__global__ void __launch_bounds__(64) k_tree_advance(DevCfg c, Tree t, Tree o, int G, const int *src_game, const int *flat, int *VL,
-                                                     int *kept, fpc_board *roots_out) {
+__global__ void __launch_bounds__(64) k_tree_advance(DevCfg c, Tree t, Tree o, int G, const int *src_game, const int *flat,
+                                                     const fpc_board *fresh, int *VL, int *kept, fpc_board *roots_out) {
   __shared__ WaveLds s;
   __shared__ int q_c0[64], q_ex[64], q_bs[64];
   const int g = blockIdx.x;
   if (g >= G) return;
   const int lane = lane_id();
-  const int sg = src_game ? src_game[g] : g, fl = flat[g];
-  const size_t ob = (size_t)sg * t.node_cap, nb = (size_t)g * t.node_cap;
-  const fpc_board *opool = t.boards + (size_t)sg * t.board_cap;
+  const int sg = src_game ? src_game[g] : g;
+  const size_t nb = (size_t)g * t.node_cap;
   fpc_board *npool = o.boards + (size_t)g * t.board_cap;
+  if (sg < 0) {                                              // a fresh row (block-uniform): k_search_init's state, no barrier
+    const uint32_t *src = reinterpret_cast<const uint32_t *>(&fresh[g]);
+    uint32_t *dst = reinterpret_cast<uint32_t *>(&npool[0]), *out = reinterpret_cast<uint32_t *>(&roots_out[g]);
+    const uint32_t w0 = src[lane], w1 = lane < 8 ? src[64 + lane] : 0u;
+    dst[lane] = w0; out[lane] = w0;
+    if (lane < 8) { dst[64 + lane] = w1; out[64 + lane] = w1; }
+    if (lane == 0) {
+      o.N[nb] = 1; o.W[nb] = 0.0; o.P[nb] = 0.f; o.mv[nb] = 0xffff; o.parent[nb] = -1; o.child0[nb] = -1; o.nch[nb] = 0;
+      o.bslot[nb] = 0;
+      if (VL != nullptr) VL[nb] = 0;
+      t.nnodes[g] = 1; t.nboards[g] = 1; t.alive[g] = 1; t.sims_done[g] = 0; t.err[g] = 0;
+      t.leaf_node[g] = -1; t.leaf_slot[g] = -1; t.leaf_turn[g] = 0; t.nlegal[g] = 0;
+      kept[g] = 1;
+    }
+    return;
+  }
+  const int fl = flat[g];
+  const size_t ob = (size_t)sg * t.node_cap;
+  const fpc_board *opool = t.boards + (size_t)sg * t.board_cap;
   // ---- the root child that was played
   const int rc0 = t.child0[ob], rnc = rc0 < 0 ? 0 : (int)t.nch[ob];
   int r = -1;

@@ -138,6 +138,7 @@ _SIGS = {
     "fpc_search_results": (C.c_int, [C.c_void_p, P(Board), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
                                      C.c_void_p, C.c_void_p, C.c_void_p]),
     "fpc_search_advance": (C.c_int, [C.c_void_p, P(C.c_int), P(C.c_int), C.c_int, P(Board), P(C.c_int)]),
+    "fpc_search_advance_refill": (C.c_int, [C.c_void_p, P(C.c_int), P(C.c_int), P(Board), C.c_int, P(Board), P(C.c_int)]),
     "fpc_search_play": (C.c_int, [C.c_void_p, C.c_double, P(C.c_double), P(C.c_int), P(C.c_int), P(Board)]),
     "fpc_search_play_ms": (C.c_int, [C.c_void_p, P(C.c_float)]),
     "fpc_search_grandchildren": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, P(C.c_int), C.c_void_p, C.c_void_p]),
@@ -410,6 +411,44 @@ class Engine:
         kept = np.zeros(n, np.int32)
         rc = self.L.fpc_search_advance(self.h, sg, C.cast(fl.ctypes.data, P(C.c_int)), n, _bp(pods) if n else None,
                                        C.cast(kept.ctypes.data, P(C.c_int)))
+        if rc == 0 or rc == -7:           # FPC_EMOVE: the other games were advanced
+            self.G = n
+        self._chk(rc)
+        if roots is not None:
+            for g, b in enumerate(roots):
+                C.memmove(C.byref(b), pods[g].ctypes.data, BOARD_BYTES)
+        return kept
+
+    def search_advance_refill(self, flats, src_games, fresh=None, roots=None, roots_np=None):
+        """subtree reuse with refill (include/fpc_engine.h fpc_search_advance_refill): search_advance in which
+        src_games[i] == -1 starts a new game in row i on fresh[i] instead (flats[i] is then ignored).  fresh: list of
+        Board or [n, 288] uint8 array, read at the -1 positions only (None where there is none); src_games None:
+        identity.  roots / roots_np receive the new root PODs.  Returns the kept visit counts (int32 [n], 1 for a fresh
+        row)."""
+        fl = np.ascontiguousarray(flats, np.int32)
+        n = int(fl.shape[0])
+        sg = None
+        if src_games is not None:
+            sa = np.ascontiguousarray(src_games, np.int32)
+            assert sa.shape == (n,)
+            sg = C.cast(sa.ctypes.data, P(C.c_int))
+        fr = None
+        if fresh is not None:
+            if isinstance(fresh, np.ndarray):
+                assert fresh.shape == (n, BOARD_BYTES) and fresh.dtype == np.uint8 and fresh.flags.c_contiguous
+                fr = _bp(fresh)
+            else:
+                assert len(fresh) == n
+                arr = (Board * n)()
+                for i, b in enumerate(fresh):
+                    if b is not None:
+                        C.memmove(C.byref(arr[i]), C.byref(b), BOARD_BYTES)
+                fr = arr
+        pods = np.zeros((n, BOARD_BYTES), np.uint8) if roots_np is None else roots_np
+        assert pods.shape == (n, BOARD_BYTES) and pods.dtype == np.uint8 and pods.flags.c_contiguous
+        kept = np.zeros(n, np.int32)
+        rc = self.L.fpc_search_advance_refill(self.h, sg, C.cast(fl.ctypes.data, P(C.c_int)), fr, n, _bp(pods) if n else None,
+                                              C.cast(kept.ctypes.data, P(C.c_int)))
         if rc == 0 or rc == -7:           # FPC_EMOVE: the other games were advanced
             self.G = n
         self._chk(rc)

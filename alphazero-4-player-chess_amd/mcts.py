@@ -139,7 +139,9 @@ class MCTS:
         starts fresh trees.  Re-roots the search this object ran last: new game i continues game keep_idx[i] of it from
         the root child flats[i], then runs num_searches simulations on the kept subtrees -- fewer where kept + new would
         pass the engine's max_sims (create the engine with 2 * num_searches, as AlphaZero.play does).  `pods` (list of
-        fpc_ffi.Board) receive the new root states.  Returns the fpc_ffi.Engine.search_results dict."""
+        fpc_ffi.Board) receive the new root states.  keep_idx[i] == -1 (selfplay.play(refill=...)) starts a new game in
+        row i instead, on the start board pods[i] (fpc_search_advance_refill; flats[i] is ignored); it shares the
+        batch-wide simulation count.  Returns the fpc_ffi.Engine.search_results dict."""
         G = len(flats)
         eng = az.engine()
         eng.set_rules(int(self.rules))
@@ -150,7 +152,11 @@ class MCTS:
             eng.set_root_noise(gamma, float(self.args["dirichlet_epsilon"]))
         else:
             eng.set_root_noise(None, 0.0)
-        kept = eng.search_advance(flats, keep_idx, roots=pods)
+        if keep_idx is not None and any(int(k) < 0 for k in keep_idx):
+            # refill (fpc_search_advance_refill): keep_idx[i] == -1 starts a new game in row i on pods[i]
+            kept = eng.search_advance_refill(flats, keep_idx, fresh=pods, roots=pods)
+        else:
+            kept = eng.search_advance(flats, keep_idx, roots=pods)
         sims = min(int(self.args["num_searches"]), eng.max_sims - (int(kept.max()) - 1))
         if self._native:
             self.sync_weights(eng)

@@ -13,6 +13,7 @@ Semantics kept from the reference:
     z = +1 if its side-to-move team != losing_team else -1 (:128-137, quirk Q12);
   * games alive after max_game_length plies are scored by the material heuristic of the side to move
     times heuristic_weight, sign by team (:161-175).
+Beyond the reference (opt-in): `refill` keeps the batch full by starting a new game in a finished game's position.
 Returned tuples are compact: (root position POD, flat[], visits[], z); dense tensors are rebuilt with
 tuples.dense_pi / engine.encode when the trainer needs them.
 """
@@ -64,8 +65,9 @@ def sample_move(flats, visits, temperature, u):
 
 
 class Episode:
-    def __init__(self, gid):
+    def __init__(self, gid, start=0):
         self.gid = gid
+        self.start = start      # the loop step of the game's first search (0 unless the game came in through `refill`)
         self.entries = []       # (board POD snapshot, flats, visits)
         self.moves = []
         self.z = []             # per entry
@@ -73,41 +75,48 @@ class Episode:
         self.length = 0
 
 
-def play(search_fn, eng, start_boards, args, uniforms, continue_fn=None, on_searched=None, device_play=False):
+def play(search_fn, eng, start_boards, args, uniforms, continue_fn=None, on_searched=None, device_play=False, refill=None):
     """search_fn(list_of_PODs) -> search_results dict (fpc_ffi.Engine.search_results layout) and
-    leaves the PODs with the piece-list order the search produced.  uniforms[ply][gid] in [0,1).
+    leaves the PODs with the piece-list order the search produced.  uniforms[ply][gid] in [0,1): the draw of game gid at
+    its OWN ply.
     continue_fn (opt-in subtree reuse, not reference semantics; None: every ply is search_fn, as in the reference):
     from the second ply on the loop calls continue_fn(keep_idx, picks_of_kept, states) instead -- keep_idx: the
     indices, within the last batch, of the games that go on (ascending), picks_of_kept: the moves they played; it
     re-roots the last search on those moves (fpc_search_advance), searches, overwrites `states` with the trees' root
     PODs and returns the same dict.  Terminal detection stays here, on this loop's own copies of the states.
-    on_searched (optional): called as on_searched(ids, ply) right after each ply's search has returned, ids = the game
-    ids of that search in batch order (AlphaZero's device replay collects the ply's tuples on the device there).
+    on_searched (optional): called as on_searched(ids, step) right after each step's search has returned, ids = the game
+    ids of that search in batch order (AlphaZero's device replay collects the step's tuples on the device there).
     device_play (opt-in, default False): the ply's moves are chosen, made and judged on the device by ONE
     eng.search_play(temperature, uniforms of the ply) on the search search_fn / continue_fn left finished, instead of
     the per-game sample_action loop, eng.take_action and eng.game_result.  The draw is sample_move's (the same child
     as sample_action's except within rounding of a boundary); everything else in this loop is as it is.
+    refill (opt-in, not reference semantics; None: the loop is the reference's, call for call): a list of further start
+    PODs.  A game that ends -- on the board, or after max_game_length plies of its OWN (z from the heuristic on the
+    state after its last move) -- hands its batch POSITION to the next board of `refill`, which becomes game
+    len(start_boards), + 1, ...; once `refill` is used up positions are deleted as before, and the loop runs until no
+    game is left.  continue_fn then gets keep_idx[i] = picks[i] = -1 at the refilled positions, with states[i] the new
+    game's start board there (fpc_search_advance_refill).  Episode.start is the step of a game's first search.
     Returns the list of finished Episodes (all games, in game-id order)."""
-    R = eng.R
     states = [fpc_ffi.clone_board(b) for b in start_boards]
     ids = list(range(len(states)))
     eps = {g: Episode(g) for g in ids}
-    T = float(args["temperature"])
-    for ply in range(int(args["max_game_length"])):
-        if not states:
-            break
-        res = search_fn(states) if continue_fn is None or ply == 0 else continue_fn(keep_pos, keep_picks, states)
+    queue = [fpc_ffi.clone_board(b) for b in refill] if refill else []
+    T, L, hw = float(args["temperature"]), int(args["max_game_length"]), float(args["heuristic_weight"])
+    step = 0
+    while states and L > 0:
+        res = search_fn(states) if continue_fn is None or step == 0 else continue_fn(keep_pos, keep_picks, states)
         if on_searched is not None:
-            on_searched(list(ids), ply)
+            on_searched(list(ids), step)
+        plies = [eps[g].length for g in ids]                     # each game's own ply
         picks = []
         for i in range(len(states)):
             n = int(res["n_children"][i])
             flats, visits = res["flat"][i, :n].copy(), res["visits"][i, :n].copy()
             eps[ids[i]].entries.append((fpc_ffi.clone_board(states[i]), flats, visits))
             if not device_play:
-                picks.append(sample_action(flats, visits, T, uniforms[ply][ids[i]]))
+                picks.append(sample_action(flats, visits, T, uniforms[plies[i]][ids[i]]))
         if device_play:
-            fl, results, pods = eng.search_play(T, [uniforms[ply][g] for g in ids])
+            fl, results, pods = eng.search_play(T, [uniforms[p][g] for p, g in zip(plies, ids)])
             if int(fl.min()) < 0:
                 raise RuntimeError("device_play: game %d has no move to play" % ids[int(fl.argmin())])
             picks = [int(f) for f in fl]
@@ -124,12 +133,17 @@ def play(search_fn, eng, start_boards, args, uniforms, continue_fn=None, on_sear
                 e.result = int(results[i])
                 losing_team = states[i].turn & 1               # team of the player who just moved (Q12)
                 e.z = [1.0 if (b.turn & 1) != losing_team else -1.0 for b, _, _ in e.entries]
+            elif e.length == L:                                  # max_game_length reached (:161-175)
+                curr_team = nxt[i].turn & 1
+                h = eng.L.fpc_board_heuristic(nxt[i], curr_team) * hw
+                e.z = [h if (b.turn & 1) == curr_team else -h for b, _, _ in e.entries]
             else:
                 keep_s.append(nxt[i]); keep_i.append(ids[i]); keep_pos.append(i); keep_picks.append(picks[i])
+                continue
+            if queue:                                            # the finished game's position goes to a new game
+                g = len(eps)
+                eps[g] = Episode(g, start=step + 1)
+                keep_s.append(queue.pop(0)); keep_i.append(g); keep_pos.append(-1); keep_picks.append(-1)
         states, ids = keep_s, keep_i
-    for s, g in zip(states, ids):                                # max_game_length reached (:161-175)
-        e = eps[g]
-        curr_team = s.turn & 1
-        h = eng.L.fpc_board_heuristic(s, curr_team) * float(args["heuristic_weight"])
-        e.z = [h if (b.turn & 1) == curr_team else -h for b, _, _ in e.entries]
+        step += 1
     return [eps[g] for g in sorted(eps)]

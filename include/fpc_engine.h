@@ -210,6 +210,31 @@ int fpc_search_set_leaves(fpc_engine *e, int leaves, double virtual_loss);
  * roots_out (nullable): the new root states; kept_visits (nullable): the new roots' visit counts. */
 int fpc_search_advance(fpc_engine *e, const int *src_game /* nullable: 0..n_games-1 */, const int *flat,
                        int n_games, fpc_board *roots_out /* nullable */, int *kept_visits /* nullable */);
+/* ---- subtree reuse with refill (opt-in; additions only, fpc_abi_version() unchanged) ---------------------------------
+ * fpc_search_advance that also STARTS games, in the same single launch: a self-play batch stays full when a finished
+ * game's row is handed to a new start position while the other rows keep their subtrees.  Needs a finished search,
+ * exactly as fpc_search_advance does (FPC_ESTATE otherwise).  New game i is one of two kinds:
+ *   src_game[i] >= 0:  it continues old game src_game[i] from the root child whose move is flat[i]; everything
+ *                      fpc_search_advance specifies holds word for word (the kept subtree, the state of a never-selected
+ *                      child, root noise on an expanded new root, FPC_EMOVE for a move that is no root child after the
+ *                      others are advanced, the out-of-place work);
+ *   src_game[i] == -1: a fresh root on fresh[i], in the state fpc_search_begin leaves a game in: N = 1, W = 0, no
+ *                      children, board slot 0 = fresh[i], one node, one board, alive, no error, sims_done = 0, no leaf and
+ *                      no pending visit; kept_visits[i] = 1, roots_out[i] = fresh[i], flat[i] is ignored.  Root noise, if
+ *                      set, reaches the root when it is expanded, from row i.
+ * src_game == NULL means identity: the call is fpc_search_advance.  fresh entries at kept positions are not read, and
+ * fresh may be NULL when there is no -1.  Old games that nobody names are dropped.  A kept game may land at a higher
+ * index than it had as well as at a lower one.  n_games may exceed the finished search's game count, up to
+ * max_games / leaves.  Afterwards the engine is in the state fpc_search_begin / fpc_search_advance leave it in, with
+ * G = n_games; max_i(kept_visits[i]) - 1 simulations count as issued (a fresh root contributes 0), and every row, fresh
+ * or kept, shares what is left of max_sims.
+ * FPC_EINVAL (nothing is uploaded or launched, the finished search stays as it was): the non-negative entries of
+ * src_game are not strictly ascending among themselves; an entry < -1 or >= G; a -1 with fresh == NULL; a fresh board
+ * fpc_search_begin would refuse; n_games < 1; leaves * n_games > max_games; root noise uploaded for another number of
+ * games. */
+int fpc_search_advance_refill(fpc_engine *e, const int *src_game /* nullable */, const int *flat,
+                              const fpc_board *fresh /* host [n_games], nullable */, int n_games,
+                              fpc_board *roots_out /* nullable */, int *kept_visits /* nullable */);
 
 /* ---- device-side move choice (opt-in): what a self-play ply does between the finished search and fpc_search_advance /
  * the next fpc_search_begin -- choose each game's move from the root's visit counts (alphazero.py:104-118), make it
