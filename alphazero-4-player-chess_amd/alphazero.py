@@ -25,6 +25,10 @@ refill (default False) -- learn() plays the num_games of an iteration as ONE run
 a finished game's batch position is taken by a new game (play(total_games=num_games), selfplay.play(refill=...)) instead
 of num_games // num_parallel_games runs that shrink to their longest game; with reuse_tree the rows that go on keep their
 subtrees beside the fresh ones (fpc_search_advance_refill).  Composes with reuse_tree, device_play and device_replay.
+sim_budget (default None; with reuse_tree) -- per-game simulation budgets for the plies that continue kept subtrees
+(mcts.budgets_for, fpc_search_set_budget): "per_game" gives every game num_searches unless its own kept visits leave less
+room, so a fresh row is no longer cut short by a kept root beside it; "visit_target" searches every root until
+num_searches simulations have gone through it, kept ones included, and needs a handle of num_searches, not twice that.
 """
 import numpy as np
 import torch
@@ -65,8 +69,11 @@ class AlphaZero:
         # args["reuse_tree"] (opt-in, default off; not reference semantics): every ply after the first continues on the
         # subtree of the move played (MCTS.continue_search) -- with the internal network or an external evaluator alike.
         # The handle then holds 2 * num_searches simulations: the visits kept from the last ply count against max_sims
+        # -- unless args["sim_budget"] = "visit_target" searches every root only up to num_searches simulations through
+        # it (mcts.budgets_for): kept + new visits then never pass num_searches, and the handle holds just that
         reuse = bool(self.args.get("reuse_tree", False)) if hasattr(self.args, "get") else False
-        return az.engine(self.mcts.engine_rows(G), int(self.args["num_searches"]) * (2 if reuse else 1), self.mcts.nn_dtype if self.mcts._native else None)
+        double = reuse and self.mcts.sim_budget != "visit_target"
+        return az.engine(self.mcts.engine_rows(G), int(self.args["num_searches"]) * (2 if double else 1), self.mcts.nn_dtype if self.mcts._native else None)
 
     def play(self, total_games=None):
         """One self-play run of num_parallel_games games; total_games (at least that many): the batch starts with

@@ -75,6 +75,10 @@ struct fpc_engine {
   int *d_adv = nullptr;           // [2][max_games] src_game | flat of one advance
   fpc_board *d_fresh = nullptr;   // [max_games] start boards of the rows fpc_search_advance_refill refills
   std::vector<fpc_board> fresh_stage;  // their host staging (the entries at kept positions are not read from the caller)
+  // ---- per-game simulation budgets (fpc_search_set_budget)
+  int *d_budget = nullptr;        // [max_games], allocated on the first call; t.budget points here while budgets are set
+  std::vector<int> base;          // [G] simulations already through each root: kept_visits - 1 after an advance, else 0
+  bool selected = false;          // a selection has been issued since the last begin / advance
   // ---- device-side move choice (fpc_search_play); allocated on the first call
   double *d_powtab = nullptr;     // [max_sims + 16] pow(v, 1 / powtab_T) by the host libm
   double powtab_T = -1.0;         // temperature the uploaded table was made for (-1: none yet)
@@ -538,6 +542,9 @@ int fpc_search_begin(fpc_engine *e, const fpc_board *roots, int n_games, double 
   HIPCHK(e, hipGetLastError());
   e->searching = true;
   e->sims_issued = 0;
+  e->base.assign((size_t)n_games, 0);
+  e->t.budget = nullptr;          // budgets belong to one ply
+  e->selected = false;
   e->stepping = true;
   e->multi = e->leaves > 1;
   e->rows_k = 1;
@@ -554,12 +561,17 @@ static int check_searching(fpc_engine *e) {
 }
 
 // admission of a call that selects, after its own argument checks: the rows of the engine's leaves per game fit, and
-// n more simulations stay within max_sims (pools + log table), which they are then counted against
+// n more simulations stay within max_sims (pools + log table), which they are then counted against.  With per-game
+// budgets set (fpc_search_set_budget) every game is bounded by base[g] + budget[g] <= max_sims instead, whatever the
+// number of steps: the batch-wide check does not apply.
 static int admit(fpc_engine *e, int n) {
   int r;
   if ((r = check_rows(e, e->leaves, e->G))) return r;
-  if (e->sims_issued + n > e->cfg.max_sims) return fail(e, FPC_ECAPACITY, "more than max_sims = %d simulations since fpc_search_begin", e->cfg.max_sims);
-  e->sims_issued += n;
+  if (!e->t.budget) {
+    if (e->sims_issued + n > e->cfg.max_sims) return fail(e, FPC_ECAPACITY, "more than max_sims = %d simulations since fpc_search_begin", e->cfg.max_sims);
+    e->sims_issued += n;
+  }
+  e->selected = true;
   return 0;
 }
 
@@ -680,6 +692,34 @@ int fpc_search_expand(fpc_engine *e, const float *logits_dev, const float *value
   HIPCHK(e, hipGetLastError());
   mark(e, 4);
   e->stats.launches_expand++;
+  return 0;
+}
+
+int fpc_search_set_budget(fpc_engine *e, const int *budget, int n_games) {
+  if (!e) return fail(e, FPC_EINVAL, "null engine");
+  if (!e->searching)
+    return fail(e, FPC_ESTATE, "fpc_search_set_budget needs a search in progress: after fpc_search_begin / fpc_search_advance(_refill)");
+  if (e->selected && e->stepping)
+    return fail(e, FPC_ESTATE, "fpc_search_set_budget: a selection has been issued since the last fpc_search_begin / fpc_search_advance");
+  if (e->selected)      // (results read right after a begin / advance, before any selection, leave the search where it was)
+    return fail(e, FPC_ESTATE, "fpc_search_set_budget: the search is finished (fpc_search_results has been read): advance it or begin another");
+  if (n_games != e->G) return fail(e, FPC_EINVAL, "fpc_search_set_budget: n_games %d, the search has %d games", n_games, e->G);
+  if (!budget) {
+    e->t.budget = nullptr;
+    return 0;
+  }
+  for (int g = 0; g < n_games; ++g)
+    if (budget[g] < 0) return fail(e, FPC_EINVAL, "fpc_search_set_budget: budget[%d] = %d is negative", g, budget[g]);
+  for (int g = 0; g < n_games; ++g)
+    if ((long)e->base[g] + budget[g] > e->cfg.max_sims)
+      return fail(e, FPC_ECAPACITY, "fpc_search_set_budget: game %d: %d simulations kept + budget %d > max_sims = %d", g, e->base[g],
+                  budget[g], e->cfg.max_sims);
+  USE_DEV(e);
+  int r;
+  if (!e->d_budget && (r = dalloc(e, &e->d_budget, (size_t)e->cfg.max_games))) return r;
+  // pageable host memory: the copy has left `budget` when the call returns
+  HIPCHK(e, hipMemcpyAsync(e->d_budget, budget, (size_t)n_games * sizeof(int), hipMemcpyHostToDevice, e->stream));
+  e->t.budget = e->d_budget;
   return 0;
 }
 
@@ -871,12 +911,16 @@ static int advance_impl(fpc_engine *e, const int *src_game, const int *flat, con
   e->multi = e->leaves > 1;
   e->rows_k = 1;
   e->pending_vl = false;
+  e->t.budget = nullptr;          // budgets belong to one ply
+  e->selected = false;
   std::vector<int> kept(n_games), errs(n_games);
   HIPCHK(e, hipMemcpyAsync(kept.data(), e->d_rc_meta, (size_t)n_games * sizeof(int), hipMemcpyDeviceToHost, e->stream));
   HIPCHK(e, hipMemcpyAsync(errs.data(), t.err, (size_t)n_games * sizeof(int), hipMemcpyDeviceToHost, e->stream));
   if (roots_out) HIPCHK(e, hipMemcpyAsync(roots_out, e->d_roots, (size_t)n_games * sizeof(fpc_board), hipMemcpyDeviceToHost, e->stream));
   HIPCHK(e, hipStreamSynchronize(e->stream));
   e->sims_issued = (long)*std::max_element(kept.begin(), kept.end()) - 1;
+  e->base.resize((size_t)n_games);
+  for (int i = 0; i < n_games; ++i) e->base[i] = std::max(kept[i] - 1, 0);     // per game, for fpc_search_set_budget
   if (kept_visits) std::copy(kept.begin(), kept.end(), kept_visits);
   return err_to_status(e, errs, "game");
 }

@@ -77,6 +77,8 @@ struct Tree {
   // root Dirichlet noise (N4; off when null): gamma draws [G][FPC_MAX_MOVES], one per root child in ascending flat order
   const float *noise;
   float noise_eps;
+  // per-game simulation budgets (fpc_search_set_budget; null: none): [G] caps on sims_done, read by select_game only
+  const int *budget;
 };
 
 // ---- LDS image of one wave --------------------------------------------------------------------
@@ -1460,8 +1462,13 @@ __device__ inline void select_game(WaveLds &s, const DevCfg &c, const Tree &t, i
   int c0 = t.child0[nb], nc = t.nch[nb], Nn = t.N[nb];
   int slot = t.bslot[nb], parent_slot = -1;        // board-pool slot of node n / of its parent
   const int nboards0 = t.nboards[g];
+  // Per-game budget (fpc_search_set_budget): descent k of a step is made only while sims_done + k < budget.  The two loads
+  // go out with the batch above -- no dependent round trip -- and without budgets (null) none is issued.  sims_done is
+  // the count at the start of the step's selection: a descent changes it only at a terminal leaf, which ends the step.
+  int room = 1;
+  if (t.budget != nullptr) room = t.budget[g] - t.sims_done[g] - (MULTI ? m->k : 0);
   if constexpr (MULTI) { m->leaf_vl = m->lp.VL[nb]; Nn += m->leaf_vl; }
-  if (!is_alive) {                          // root already removed from the search (Q5)
+  if (!is_alive || room <= 0) {             // root already removed from the search (Q5), or the game is at its budget: a dead row
     if (lane == 0) { leaf_node[FPC_ROW] = -1; leaf_slot[FPC_ROW] = -1; }
     return;
   }
@@ -1616,7 +1623,8 @@ __device__ inline void select_game(WaveLds &s, const DevCfg &c, const Tree &t, i
 constexpr OneLeaf *ONE_LEAF = nullptr;
 
 // K descents of one game in one step (leaf-parallel search): row k*G + g for k = 0, 1, ...  The first row that is not
-// live (collision, terminal leaf, dead game) ends the game's selection for this step; its remaining rows are dead.
+// live (collision, terminal leaf, dead game, the game's budget reached) ends the game's selection for this step; its
+// remaining rows are dead.
 __device__ inline void select_game_multi(WaveLds &s, const DevCfg &c, const Tree &t, int G, int g, int K, double Cpuct,
                                          const double *logtab, bool to_next, const LeafPar &lp) {
   int k = 0;

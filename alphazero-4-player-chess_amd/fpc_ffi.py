@@ -139,6 +139,7 @@ _SIGS = {
                                      C.c_void_p, C.c_void_p, C.c_void_p]),
     "fpc_search_advance": (C.c_int, [C.c_void_p, P(C.c_int), P(C.c_int), C.c_int, P(Board), P(C.c_int)]),
     "fpc_search_advance_refill": (C.c_int, [C.c_void_p, P(C.c_int), P(C.c_int), P(Board), C.c_int, P(Board), P(C.c_int)]),
+    "fpc_search_set_budget": (C.c_int, [C.c_void_p, P(C.c_int), C.c_int]),
     "fpc_search_play": (C.c_int, [C.c_void_p, C.c_double, P(C.c_double), P(C.c_int), P(C.c_int), P(Board)]),
     "fpc_search_play_ms": (C.c_int, [C.c_void_p, P(C.c_float)]),
     "fpc_search_grandchildren": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, P(C.c_int), C.c_void_p, C.c_void_p]),
@@ -456,6 +457,18 @@ class Engine:
             for g, b in enumerate(roots):
                 C.memmove(C.byref(b), pods[g].ctypes.data, BOARD_BYTES)
         return kept
+
+    def search_set_budget(self, budget):
+        """per-game simulation budgets of the search in progress (include/fpc_engine.h fpc_search_set_budget): budget[g]
+        caps the simulations game g completes in this search (sims_done[g]); a game at its budget selects nothing.  Set
+        after search_begin / search_advance(_refill) and before the search's first selection; None clears them, and so
+        does every later begin / advance.  The step count stays the caller's: run max(budget) simulations."""
+        if budget is None:
+            self._chk(self.L.fpc_search_set_budget(self.h, None, self.G))
+            return
+        b = np.ascontiguousarray(budget, np.int32)
+        assert b.ndim == 1
+        self._chk(self.L.fpc_search_set_budget(self.h, C.cast(b.ctypes.data, P(C.c_int)), int(b.shape[0])))
 
     def search_finish(self):
         """fpc_search_results with every array NULL: waits for the search, reads the games' error words (raises on one)

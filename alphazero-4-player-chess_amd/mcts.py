@@ -17,6 +17,11 @@ Leaf-parallel search (opt-in, not reference semantics; include/fpc_engine.h fpc_
 args["leaves_per_step"] = K > 1 selects up to K leaves per game per simulation step, kept apart by
 args["virtual_loss"] (default 1.0); the engine then has K*G rows and the evaluator sees [K*G,24,R,R]
 (row k*G + g = the k-th leaf of game g), num_searches leaves in ceil(num_searches / K) steps.
+
+Per-game simulation budgets (opt-in, not reference semantics; include/fpc_engine.h fpc_search_set_budget):
+args["sim_budget"] = "per_game" | "visit_target" makes continue_search give every game its own simulation count
+(budgets_for) instead of the batch-wide one; search(games, budgets=...) / continue_search(..., budgets=...) take an
+explicit per-game list.  Absent / None: no budget is ever set.
 """
 import math
 
@@ -46,6 +51,26 @@ def _on_engine_device(m, eng):
     return all(t.device.type == "cuda" and t.device.index == eng.device for t in itertools.chain(m.parameters(), m.buffers()))
 
 
+SIM_BUDGET_MODES = (None, "per_game", "visit_target")
+
+
+def budgets_for(kept, num_searches, max_sims, mode):
+    """Per-game simulation budgets of one ply (fpc_search_set_budget) from the roots' kept visit counts (1 for a fresh
+    root, so kept - 1 simulations have gone through a root already); None for mode None.
+    "per_game":     min(num_searches, max_sims - (kept - 1)): every game gets num_searches unless ITS OWN kept visits
+                    leave less room in the handle -- a fresh row gets its full count beside any kept root.
+    "visit_target": max(0, num_searches - (kept - 1)): every root is searched until num_searches simulations have gone
+                    through it (kept + new <= num_searches, so a handle of num_searches simulations is enough)."""
+    if mode not in SIM_BUDGET_MODES:
+        raise ValueError("sim_budget must be one of %r, not %r" % (SIM_BUDGET_MODES, mode))
+    if mode is None:
+        return None
+    S, M = int(num_searches), int(max_sims)
+    if mode == "per_game":
+        return [max(0, min(S, M - (int(k) - 1))) for k in kept]
+    return [max(0, S - (int(k) - 1)) for k in kept]
+
+
 class MCTS:
     def __init__(self, gameType, neural_net, args):
         self.gameType = gameType
@@ -71,6 +96,10 @@ class MCTS:
         # args["device_weights"] = True (opt-in): a module that lies on the engine's GPU is packed into the engine there
         # (fpc_load_weights_device: no host copy, in place); any other module takes the host path as before
         self.device_weights = bool(args.get("device_weights", False)) if hasattr(args, "get") else False
+        # args["sim_budget"] (opt-in): None | "per_game" | "visit_target" -- continue_search's per-game budgets (budgets_for)
+        self.sim_budget = args.get("sim_budget", None) if hasattr(args, "get") else None
+        if self.sim_budget not in SIM_BUDGET_MODES:
+            raise ValueError("sim_budget must be one of %r, not %r" % (SIM_BUDGET_MODES, self.sim_budget))
 
     def engine_rows(self, G):
         """rows of the engine handle a search of G games needs (G * leaves_per_step)"""
@@ -99,7 +128,9 @@ class MCTS:
         return policy * (1.0 - eps) + noise * eps
 
     @torch.no_grad()
-    def search(self, games):
+    def search(self, games, budgets=None):
+        """budgets (optional): per-game simulation counts of this search (fpc_search_set_budget), each at most
+        num_searches -- game g completes budgets[g] simulations while the batch runs max(budgets) steps' worth."""
         G = len(games)
         sims = int(self.args["num_searches"])
         eng = az.engine(self.engine_rows(G), sims, self.nn_dtype if self._native else None)
@@ -113,6 +144,10 @@ class MCTS:
         else:
             eng.set_root_noise(None, 0.0)
         eng.search_begin(pods, float(self.args["C"]))
+        if budgets is not None:
+            budgets = [int(b) for b in budgets]
+            eng.search_set_budget(budgets)
+            sims = max(budgets)
         if self._native:
             self.sync_weights(eng)
             eng.set_policy_mode(self.policy_head == "legal")
@@ -133,7 +168,7 @@ class MCTS:
         return roots
 
     @torch.no_grad()
-    def continue_search(self, pods, keep_idx, flats):
+    def continue_search(self, pods, keep_idx, flats, budgets=None):
         """Opt-in subtree reuse (not reference semantics; include/fpc_engine.h fpc_search_advance), for callers that know
         the moves played -- selfplay.play(continue_fn=...); the drop-in search(games) carries no move history and always
         starts fresh trees.  Re-roots the search this object ran last: new game i continues game keep_idx[i] of it from
@@ -141,7 +176,10 @@ class MCTS:
         pass the engine's max_sims (create the engine with 2 * num_searches, as AlphaZero.play does).  `pods` (list of
         fpc_ffi.Board) receive the new root states.  keep_idx[i] == -1 (selfplay.play(refill=...)) starts a new game in
         row i instead, on the start board pods[i] (fpc_search_advance_refill; flats[i] is ignored); it shares the
-        batch-wide simulation count.  Returns the fpc_ffi.Engine.search_results dict."""
+        batch-wide simulation count.
+        With args["sim_budget"] set, or an explicit `budgets` list (which overrides the mode), every game gets its own
+        simulation count instead (budgets_for / fpc_search_set_budget) and the batch runs max(budget) steps' worth.
+        Returns the fpc_ffi.Engine.search_results dict."""
         G = len(flats)
         eng = az.engine()
         eng.set_rules(int(self.rules))
@@ -157,7 +195,14 @@ class MCTS:
             kept = eng.search_advance_refill(flats, keep_idx, fresh=pods, roots=pods)
         else:
             kept = eng.search_advance(flats, keep_idx, roots=pods)
-        sims = min(int(self.args["num_searches"]), eng.max_sims - (int(kept.max()) - 1))
+        if budgets is None:
+            budgets = budgets_for(kept, int(self.args["num_searches"]), eng.max_sims, self.sim_budget)
+        if budgets is not None:
+            budgets = [int(b) for b in budgets]
+            eng.search_set_budget(budgets)
+            sims = max(budgets)
+        else:
+            sims = min(int(self.args["num_searches"]), eng.max_sims - (int(kept.max()) - 1))
         if self._native:
             self.sync_weights(eng)
             eng.set_policy_mode(self.policy_head == "legal")

@@ -235,6 +235,32 @@ int fpc_search_advance(fpc_engine *e, const int *src_game /* nullable: 0..n_game
 int fpc_search_advance_refill(fpc_engine *e, const int *src_game /* nullable */, const int *flat,
                               const fpc_board *fresh /* host [n_games], nullable */, int n_games,
                               fpc_board *roots_out /* nullable */, int *kept_visits /* nullable */);
+/* ---- per-game simulation budgets (opt-in; additions only, fpc_abi_version() unchanged) ------------------------------
+ * fpc_search_run(sims) and the step entry points give every game of the batch the same number of simulations.  A budget
+ * caps them per game: budget[g] bounds sims_done[g], the simulations game g COMPLETES in this search (expansions plus
+ * terminal backups: the number fpc_search_results reports).  A game whose sims_done has reached its budget selects no
+ * leaf: its row is dead for the step (leaf_node = leaf_slot = -1), exactly as the row of a root that Q5 removed is,
+ * and nothing else about the game changes -- it stays alive, carries no error, and nothing in its tree, its pools or its
+ * counters is written.  Leaf-parallel search: descent k (0-based) of a step is made only while
+ * sims_done[g] + k < budget[g], with sims_done as it stands when the step's selection starts; the game's remaining rows
+ * of the step are dead rows.  The gate is exact: a game never completes more than budget[g] simulations, also when K does
+ * not divide it; budget[g] == 0 selects nothing.
+ * Applies to the search in progress: call it after fpc_search_begin, fpc_search_advance or fpc_search_advance_refill and
+ * before that search's first selection.  budget == NULL clears the budgets; so does every later fpc_search_begin /
+ * fpc_search_advance(_refill): budgets belong to one ply.
+ * Step counts stay the caller's: fpc_search_run(sims) still runs ceil(sims / K) steps and the step entry points as many
+ * as they are called for -- the budget only idles rows, so pass max_g budget[g]; further steps are harmless (every row is
+ * dead).  Under strict rules the batch-wide rotation (Q6) is that of the first LIVE row; a budget-idle row is not live.
+ * Capacity is per game while budgets are set.  base[g] = kept_visits[g] - 1 after an advance (0 for a fresh row) and 0
+ * after fpc_search_begin; FPC_ECAPACITY when base[g] + budget[g] > max_sims for some g (the message names the first such
+ * game; nothing changes).  While budgets are set the selecting calls do not apply the batch-wide
+ * "issued + n <= max_sims" check: each game is bounded by its own budget, which is what the log table, the node pool, the
+ * board pool and the path buffer need.  fpc_search_run still refuses sims > max_sims.
+ * FPC_ESTATE: no search in progress; a selection has been issued since the last begin / advance; a finished search whose
+ * results have been read and which was not advanced (reading the results right after a begin / advance, before any
+ * selection, changes nothing and closes nothing).  FPC_EINVAL (nothing uploaded, no state changed): null engine,
+ * n_games != the search's game count, a negative entry. */
+int fpc_search_set_budget(fpc_engine *e, const int *budget /* host [n_games], nullable */, int n_games);
 
 /* ---- device-side move choice (opt-in): what a self-play ply does between the finished search and fpc_search_advance /
  * the next fpc_search_begin -- choose each game's move from the root's visit counts (alphazero.py:104-118), make it
