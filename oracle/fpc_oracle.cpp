@@ -697,10 +697,27 @@ void orc_encode(const orc_board *boards, int n, int R, float *out) {
   }
 }
 
+// ---- TEST-ONLY single faults of the prior arithmetic (tests/test_prior_range_cpu.py proves its cases able to fail
+// with them; 0 = off, the default, and nothing else ever sets it).  1: the results of the three products (2^k scale,
+// s_c * exp(m_c - m), exp(l - m) * (1/S)) flushed to zero when subnormal;  2: subnormal operands of the legal mass and
+// of the final division read as zero;  3: the flush threshold of the exp at -87;  4: p * (1/T) in place of p / T;
+// 5: the in-chunk sum sequential instead of the butterfly;  6: the partial tail chunk's record taken over all 1024
+// slots, the gap read as logits of zero;  7: neither -inf guard (an all -inf chunk's sum and its term) ----
+static int g_prior_fault = 0;
+void orc_set_prior_fault(int fault) { g_prior_fault = fault; }
+static inline bool is_subnormal(float x) { return x != 0.f && __builtin_fabsf(x) < std::numeric_limits<float>::min(); }
+static inline float prod_out(float x) { return g_prior_fault == 1 && is_subnormal(x) ? 0.f * x : x; }
+static inline float operand_in(float x) { return g_prior_fault == 2 && is_subnormal(x) ? 0.f * x : x; }
+static inline float prior_div(float p, float T) {
+  p = operand_in(p); T = operand_in(T);
+  if (g_prior_fault == 4) { const float inv = 1.0f / T; return p * inv; }
+  return p / T;
+}
+
 // ---- deterministic exp (shared numeric spec, DESIGN.md "fpc_expf") ----
 float orc_expf(float x) {
   if (x != x) return x;
-  if (x < -86.0f) return 0.0f;
+  if (x < (g_prior_fault == 3 ? -87.0f : -86.0f)) return 0.0f;
   if (x > 88.0f) return std::numeric_limits<float>::infinity();
   float k = __builtin_rintf(x * 0x1.715476p+0f);
   float r = __builtin_fmaf(k, -0x1.62e4p-1f, x);
@@ -717,7 +734,7 @@ float orc_expf(float x) {
   uint32_t bits = (uint32_t)(ki + 127) << 23;
   float s;
   memcpy(&s, &bits, 4);
-  return p * s;
+  return prod_out(p * s);
 }
 
 // mcts.py:67-76.  Numeric spec ("policy head-to-prior arithmetic"):
@@ -734,18 +751,26 @@ int orc_policy_priors(const float *logits, int R, int turn0, const int *legal_fl
   const int ngroups = A / 4, nchunks = (ngroups + 255) / 256;
   std::vector<float> mc(nchunks), sc(nchunks);
   for (int c = 0; c < nchunks; ++c) {
+    const bool gap0 = g_prior_fault == 6;          // fault 6: the slots behind the row's end count as logits of zero
+    auto at = [&](int q, int k) { return q < ngroups ? logits[4 * q + k] : 0.f; };
     float m = NINF;
     for (int t = 0; t < 256; ++t) {
       const int q = c * 256 + t;
-      if (q >= ngroups) continue;
-      for (int k = 0; k < 4; ++k) { const float v = logits[4 * q + k]; if (v != v) has_nan = true; if (v > m) m = v; }
+      if (q >= ngroups && !gap0) continue;
+      for (int k = 0; k < 4; ++k) { const float v = at(q, k); if (v != v) has_nan = true; if (v > m) m = v; }
     }
     float part[256];
     for (int t = 0; t < 256; ++t) {
       const int q = c * 256 + t;
       part[t] = 0.f;
-      if (q < ngroups && m > NINF)
-        for (int k = 0; k < 4; ++k) part[t] = part[t] + orc_expf(logits[4 * q + k] - m);
+      if ((q < ngroups || gap0) && (m > NINF || g_prior_fault == 7))
+        for (int k = 0; k < 4; ++k) part[t] = part[t] + orc_expf(at(q, k) - m);
+    }
+    if (g_prior_fault == 5) {                      // fault 5: one running sum over the chunk
+      float run = 0.f;
+      for (int t = 0; t < 256; ++t) run = run + part[t];
+      mc[c] = m; sc[c] = run;
+      continue;
     }
     for (int w = 0; w < 4; ++w)
       for (int off = 32; off >= 1; off >>= 1) {
@@ -759,17 +784,17 @@ int orc_policy_priors(const float *logits, int R, int turn0, const int *legal_fl
   float m = NINF;
   for (int c = 0; c < nchunks; ++c) if (mc[c] > m) m = mc[c];
   float S = 0.f;
-  for (int c = 0; c < nchunks; ++c) S = S + (mc[c] > NINF ? sc[c] * orc_expf(mc[c] - m) : 0.f);
+  for (int c = 0; c < nchunks; ++c) S = S + (mc[c] > NINF || g_prior_fault == 7 ? prod_out(sc[c] * orc_expf(mc[c] - m)) : 0.f);
   float inv = 1.0f / S;
   float T = 0.f;
   for (int j = 0; j < n_legal; ++j) {
     int plane = legal_flat[j] / RR, pos = legal_flat[j] % RR;
     int src = plane * RR + rot90_src(R, -turn0, pos / R, pos % R);
-    priors[j] = orc_expf(logits[src] - m) * inv;
-    T = T + priors[j];
+    priors[j] = prod_out(orc_expf(logits[src] - m) * inv);
+    T = T + operand_in(priors[j]);
   }
   if (has_nan || !(T > 0.f) || T != T) return 1;
-  for (int j = 0; j < n_legal; ++j) priors[j] = priors[j] / T;
+  for (int j = 0; j < n_legal; ++j) priors[j] = prior_div(priors[j], T);
   return 0;
 }
 
@@ -792,10 +817,10 @@ int orc_policy_priors_legal(const float *logits, int R, int turn0, const int *le
   float T = 0.f;
   for (int j = 0; j < n_legal; ++j) {
     priors[j] = m > NINF ? orc_expf(l[j] - m) : 0.f;
-    T = T + priors[j];
+    T = T + operand_in(priors[j]);
   }
   if (has_nan || !(T > 0.f)) return 1;
-  for (int j = 0; j < n_legal; ++j) priors[j] = priors[j] / T;
+  for (int j = 0; j < n_legal; ++j) priors[j] = prior_div(priors[j], T);
   return 0;
 }
 

@@ -107,6 +107,9 @@ int  orc_policy_priors(const float *logits, int R, int turn0, const int *legal_f
  * legal logit is -inf), T = sequential ascending sum, priors p_j / T.  returns 1 on a NaN among them or not T > 0. */
 int  orc_policy_priors_legal(const float *logits, int R, int turn0, const int *legal_flat, int n_legal,
                              float *priors);
+/* TEST-ONLY: one single fault (1..7, listed at its definition) in the arithmetic of the two functions above and of
+ * orc_expf; 0 = off, the default.  tests/test_prior_range_cpu.py proves with it that its cases can fail. */
+void orc_set_prior_fault(int fault);
 
 /* ---- MCTS.search (mcts.py:17-43 + node.cpp) ---- */
 typedef struct orc_search_out {

@@ -59,6 +59,7 @@ def lib():
         L.orc_policy_priors.argtypes = [C.POINTER(C.c_float), C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int,
                                         C.POINTER(C.c_float)]
         L.orc_policy_priors_legal.argtypes = L.orc_policy_priors.argtypes
+        L.orc_set_prior_fault.argtypes = [C.c_int]
         _lib = L
     return _lib
 
@@ -87,6 +88,19 @@ def board_from_dict(R, turn, entries, castle=None):
 def set_rules(rules):
     """N4: non-strict rule set, bits as FPC_RULES_* (0 = the reference)"""
     lib().orc_set_rules(int(rules))
+
+
+PRIOR_FAULTS = {1: "products flushed to zero when subnormal", 2: "subnormal operands read as zero",
+                3: "flush threshold of the exp at -87", 4: "p * (1/T) in place of p / T",
+                5: "in-chunk sum sequential, not the butterfly", 6: "tail chunk's record over 1024 slots, zeros in the gap",
+                7: "an all -inf chunk not skipped"}
+
+
+def set_prior_fault(fault):
+    """TEST-ONLY: one single fault of the prior arithmetic (PRIOR_FAULTS; 0 = off, the default) in orc_policy_priors,
+    orc_policy_priors_legal and orc_expf -- so that tests can prove that their cases are able to fail"""
+    assert fault == 0 or fault in PRIOR_FAULTS
+    lib().orc_set_prior_fault(int(fault))
 
 
 _noise_keep = None

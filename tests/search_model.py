@@ -71,6 +71,8 @@ class Model:
         # per simulation step: {"rows", "dead": the rows without a leaf to expand (terminal leaf, collision, game over),
         # "pairs": (live row, legal move) pairs, "turns": the live rows' sides to move, "max_legal"}
         self.steps = []
+        # a list: every expansion appends (the leaf is a root, its logits row, rotation, legal list) -- tests/prior_cases.py
+        self.expansions = None
         self.noise, self.noise_eps = None, noise_eps
         self.roots = [_Node(0.0, -1, None, state=b) for b in boards]
         self.alive = [True] * len(boards)
@@ -185,6 +187,8 @@ class Model:
                     r = k * G + g
                     rot = nd.state.turn if rules & RULES_ROTATION else turn0
                     prc, pri = _priors(logits[r], R, rot, legal, self.policy_head)
+                    if self.expansions is not None:
+                        self.expansions.append((nd is self.roots[g], logits[r].copy(), rot, legal))
                     if prc:
                         return -3
                     if self.noise is not None and nd is self.roots[g]:

@@ -174,12 +174,15 @@ def test_survey_kats():
 
 def test_expf_accuracy():
     L = orc.lib()
-    xs = np.concatenate([np.linspace(-85.9, 0, 20001), -np.logspace(-8, 1.9, 2000)]).astype(np.float32)
+    # the last tenth in front of the flush threshold has a grid of its own: -86 itself is still in the domain
+    xs = np.concatenate([np.linspace(-85.9, 0, 20001), -np.logspace(-8, 1.9, 2000), np.linspace(-86.0, -85.9, 2001)]).astype(np.float32)
     got = np.array([L.orc_expf(float(x)) for x in xs], dtype=np.float32)
     ref = np.exp(xs.astype(np.float64))
     rel = np.abs(got.astype(np.float64) - ref) / ref
     assert rel.max() < 2.5e-7          # <= ~2 ulp
     assert L.orc_expf(0.0) == 1.0 and L.orc_expf(float("-inf")) == 0.0 and L.orc_expf(-90.0) == 0.0
+    # the first f32 below -86 is flushed, -86 is not
+    assert L.orc_expf(float(np.nextafter(np.float32(-86), np.float32(-np.inf)))) == 0.0 and L.orc_expf(-86.0) > 0.0
 
 
 @pytest.mark.parametrize("R", [8, 14])

@@ -432,11 +432,14 @@ DENSE = ("dense_int", "dense_scaled")
 class Tail:
     """the Linear sections of an exported blob and the header words that describe them.  kind: "identity" | "perm" |
     "dense_int" (dense_weights, value Linear = value_vector) | "dense_scaled" (dense_weights times 2^-s, exact in both
-    operand types; the value Linear all zero, so the value is tanh(0))"""
-    def __init__(self, R, dtype, layout, kind, s=0):
+    operand types; the value Linear all zero, so the value is tanh(0)) | "bias_row" (policy weights all zero, the policy
+    bias a chosen f32 row -- zero as exported, with_bias() puts a row in --, the value Linear all zero: behind ANY tower
+    with finite activations every leaf's logits are the row, bit for bit, and the value is tanh(0))"""
+    def __init__(self, R, dtype, layout, kind, s=0, bias_row=None):
         A_ch, RR = 8 * R + 8, R * R
         A = A_ch * RR
-        assert kind in ("identity", "perm") + DENSE and (s == 0 or kind == "dense_scaled")
+        assert kind in ("identity", "perm", "bias_row") + DENSE and (s == 0 or kind == "dense_scaled")
+        assert bias_row is None or kind == "bias_row"
         m = net.ResNet(stub_spec(R), 0, 64, "cpu")
         fc = torch.nn.utils.skip_init(torch.nn.Linear, A, A)
         with torch.no_grad():
@@ -458,7 +461,12 @@ class Tail:
             else:
                 fc.weight.zero_()
                 fc.bias.zero_()
-                if kind == "identity":
+                if kind == "bias_row":
+                    vfc.weight.zero_()
+                    vfc.bias.zero_()
+                    if bias_row is not None:
+                        fc.bias.copy_(torch.from_numpy(np.asarray(bias_row, np.float32)))
+                elif kind == "identity":
                     fc.weight.diagonal().fill_(1.0)
                 else:
                     perm, scale = permutation(R)
@@ -470,6 +478,19 @@ class Tail:
         assert (magic, version, r, F, nb, dt, a_ch, lay) == (b"FPCW", 3, R, 64, 0, dtype, A_ch, layout)
         self.R, self.dtype, self.layout, self.kind, self.s = R, dtype, layout, kind, s
         self.bytes = blob[head_len(64, 0):]
+
+    def with_bias(self, row):
+        """a copy of a "bias_row" Tail whose policy bias is the f32 row [A], any bit patterns (the blob carries the bias
+        as f32 [Np] right behind the [Np][Kp] 16-bit weights; held against a plain export by tests/test_prior_range_cpu.py)"""
+        import copy
+        assert self.kind == "bias_row"
+        row = np.ascontiguousarray(row, np.float32)
+        fb = np.zeros(self.Np, np.float32)
+        fb[:row.size] = row
+        off = self.Np * self.Kp * 2
+        t = copy.copy(self)
+        t.bytes = self.bytes[:off] + fb.tobytes() + self.bytes[off + 4 * self.Np:]
+        return t
 
 
 _tails = {}
