@@ -1570,7 +1570,7 @@ int fpc_set_policy_mode(fpc_engine *e, int mode) {
 }
 
 int fpc_set_rules(fpc_engine *e, int rules) {
-  if (!e || rules < 0 || rules > FPC_RULES_FIXED) return fail(e, FPC_EINVAL, "bad rule set");
+  if (!e || rules < 0 || rules > FPC_RULES_TRAINING) return fail(e, FPC_EINVAL, "bad rule set");
   if (e->searching && rules != e->dc.rules) e->searching = false;     // a search in flight was started under the other rules
   e->dc.rules = rules;
 #ifndef FPC_EMUL

@@ -1595,9 +1595,15 @@ __device__ inline void select_game(WaveLds &s, const DevCfg &c, const Tree &t, i
   if (lane == 0 && s.errbits) t.err[g] |= s.errbits;
   if (res != FPC_IN_PROGRESS) {              // node.cpp:31-42: back up 0 / -1, drop the root (Q5)
     if (lane == 0) {
-      backprop_lane0(t, nb, n, res == FPC_STALEMATE ? 0.0f : -1.0f);
+      float v = res == FPC_STALEMATE ? 0.0f : -1.0f;
+      bool leaves = true;
+      if (c.rules & FPC_RULES_TERMINAL) {    // value by result, seen from the leaf's side to move; only a terminal ROOT leaves the search
+        if (res != FPC_STALEMATE) v = (res == FPC_WIN_BG ? 1 : 0) == (s.b.turn & 1) ? 1.0f : -1.0f;
+        leaves = n == 0;
+      }
+      backprop_lane0(t, nb, n, v);
       t.sims_done[g] += 1;
-      t.alive[g] = 0;
+      if (leaves) t.alive[g] = 0;
       leaf_node[FPC_ROW] = -1;
       leaf_slot[FPC_ROW] = -1;
     }

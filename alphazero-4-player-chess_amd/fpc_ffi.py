@@ -17,6 +17,7 @@ MAX_SQ, MAX_PL, NO_SQ, MAX_MOVES = 196, 16, 255, 256
 MAX_LEAVES = 8                          # FPC_MAX_LEAVES: leaves per game per step of a leaf-parallel search
 REPLAY_RINGS, REPLAY_SCRATCH, REPLAY_COLLECTED, REPLAY_GATHERED = 2, 2, 0, 1     # FPC_REPLAY_*: ring 0 experience, 1 validation
 RULES_STRICT, RULES_PUCT, RULES_ROTATION, RULES_PLANES, RULES_FULL_MOVES, RULES_FIXED = 0, 1, 2, 4, 8, 15
+RULES_TERMINAL, RULES_TRAINING = 16, 31   # Q5 + the terminal value (search past terminal leaves, value by result); FIXED | TERMINAL
 
 
 class Board(C.Structure):
@@ -606,7 +607,8 @@ class Engine:
 
     # ---- N4: non-strict rule set and root Dirichlet noise (include/fpc_engine.h FPC_RULES_*) ----
     def set_rules(self, rules):
-        """0 = strict reference semantics (default); RULES_FIXED = all corrections"""
+        """0 = strict reference semantics (default); RULES_FIXED = the four corrections of selection, rotation, planes and
+        moves; RULES_TRAINING = those plus RULES_TERMINAL (a terminal leaf is valued by its result and the search goes on)"""
         self._chk(self.L.fpc_set_rules(self.h, int(rules)))
 
     def set_leaves(self, k, virtual_loss=1.0):

@@ -84,11 +84,12 @@ class MCTS:
         self._native = _is_resnet(neural_net)
         # N4 (explicitly NOT part of parity with the reference): args["rules"] = "strict"
         # (default: every quirk of the reference, bit-exact) or "fixed" (AlphaZero PUCT with the child's value
-        # negated, per-sample rotation, un-shifted input planes, full moves in the tree), or an int of
-        # fpc_ffi.RULES_* bits; args["root_noise"] = True applies Dirichlet(dirichlet_alpha) noise with weight
+        # negated, per-sample rotation, un-shifted input planes, full moves in the tree), "training" ("fixed" plus
+        # fpc_ffi.RULES_TERMINAL: a terminal leaf is valued by its result and no longer takes the root out of the
+        # search), or an int of fpc_ffi.RULES_* bits; args["root_noise"] = True applies Dirichlet(dirichlet_alpha) noise with weight
         # dirichlet_epsilon to the root priors inside the fused search loop, seeded by args["noise_seed"].
         rules = args.get("rules", "strict") if hasattr(args, "get") else "strict"
-        self.rules = {"strict": 0, "fixed": 15}.get(rules, rules)
+        self.rules = {"strict": 0, "fixed": 15, "training": 31}.get(rules, rules)
         self.root_noise = bool(args.get("root_noise", False)) if hasattr(args, "get") else False
         self._noise_rng = np.random.default_rng(int(args.get("noise_seed", 0))) if self.root_noise else None
         self.leaves = int(args.get("leaves_per_step", 1)) if hasattr(args, "get") else 1

@@ -75,7 +75,8 @@ class Episode:
         self.length = 0
 
 
-def play(search_fn, eng, start_boards, args, uniforms, continue_fn=None, on_searched=None, device_play=False, refill=None):
+def play(search_fn, eng, start_boards, args, uniforms, continue_fn=None, on_searched=None, device_play=False, refill=None,
+         z_from_result=False):
     """search_fn(list_of_PODs) -> search_results dict (fpc_ffi.Engine.search_results layout) and
     leaves the PODs with the piece-list order the search produced.  uniforms[ply][gid] in [0,1): the draw of game gid at
     its OWN ply.
@@ -96,6 +97,10 @@ def play(search_fn, eng, start_boards, args, uniforms, continue_fn=None, on_sear
     len(start_boards), + 1, ...; once `refill` is used up positions are deleted as before, and the loop runs until no
     game is left.  continue_fn then gets keep_idx[i] = picks[i] = -1 at the refilled positions, with states[i] the new
     game's start board there (fpc_search_advance_refill).  Episode.start is the step of a game's first search.
+    z_from_result (opt-in, not reference semantics; default False: Q12): a game that ends on the board with result r
+    labels its entries by r, as FPC_RULES_TERMINAL values a terminal leaf -- 0.0 for a stalemate, else +1.0 where the
+    entry's side-to-move team is the winner (WIN_RY: team 0, WIN_BG: team 1) and -1.0 where it is not.  The
+    max_game_length branch is untouched.
     Returns the list of finished Episodes (all games, in game-id order)."""
     states = [fpc_ffi.clone_board(b) for b in start_boards]
     ids = list(range(len(states)))
@@ -131,8 +136,14 @@ def play(search_fn, eng, start_boards, args, uniforms, continue_fn=None, on_sear
             e.length += 1
             if results[i] != 0:
                 e.result = int(results[i])
-                losing_team = states[i].turn & 1               # team of the player who just moved (Q12)
-                e.z = [1.0 if (b.turn & 1) != losing_team else -1.0 for b, _, _ in e.entries]
+                if z_from_result and e.result == 3:            # FPC_STALEMATE
+                    e.z = [0.0 for _ in e.entries]
+                elif z_from_result:
+                    winner = 0 if e.result == 1 else 1         # FPC_WIN_RY: team 0, FPC_WIN_BG: team 1
+                    e.z = [1.0 if (b.turn & 1) == winner else -1.0 for b, _, _ in e.entries]
+                else:
+                    losing_team = states[i].turn & 1           # team of the player who just moved (Q12)
+                    e.z = [1.0 if (b.turn & 1) != losing_team else -1.0 for b, _, _ in e.entries]
             elif e.length == L:                                  # max_game_length reached (:161-175)
                 curr_team = nxt[i].turn & 1
                 h = eng.L.fpc_board_heuristic(nxt[i], curr_team) * hw

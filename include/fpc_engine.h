@@ -165,7 +165,20 @@ enum {
   FPC_RULES_ROTATION = 2,    /* Q6: every sample is rotated by its OWN side to move (encode and policy decode)       board.cpp:322,354-355 */
   FPC_RULES_PLANES = 4,      /* Q7: input plane 6*rel_colour + type, no -1 wrap                                       board.cpp:336 */
   FPC_RULES_FULL_MOVES = 8,  /* Q9: tree/self-play moves promote (to a queen), hop the rook when castling, update rights  node.cpp:87-92 */
-  FPC_RULES_FIXED = 15
+  FPC_RULES_FIXED = 15,
+  /* Q5 + the terminal value (node.cpp:31-42, mcts.py:20-25).  Independent of the four bits above; when a descent ends on
+   * a leaf whose GetGameResult is not FPC_IN_PROGRESS:
+   *   value   backed up along the path, leaf first, sign alternating as ever: 0 for FPC_STALEMATE, else +1 if the winning
+   *           team (FPC_WIN_RY -> 0, FPC_WIN_BG -> 1) is the leaf's side-to-move team (turn & 1), else -1 (clear: 0 / -1,
+   *           which calls "its first legal move takes a king" a loss of the side to move);
+   *   search  the game STAYS in the search (clear: it leaves it).  The row is dead for this step, sims_done += 1, a
+   *           leaf-parallel step's selection of that game ends there with no pending visit added, and the next step
+   *           selects again; every further visit of the same terminal leaf backs up again (N += 1, W += +-v).  No second
+   *           descent within a step.  A terminal ROOT still leaves the search (it can never have a child), with the value
+   *           above.  Budgets and max_sims count terminal backups as before.
+   * After a search, alive == 0 then means an error or a terminal root. */
+  FPC_RULES_TERMINAL = 16,
+  FPC_RULES_TRAINING = 31    /* FPC_RULES_FIXED | FPC_RULES_TERMINAL */
 };
 int fpc_set_rules(fpc_engine *e, int rules);
 /* Root noise for the NEXT searches (mcts.py:45-56 defines add_dirichlet_noise and never calls it):
