@@ -79,6 +79,10 @@ struct fpc_engine {
   int *d_budget = nullptr;        // [max_games], allocated on the first call; t.budget points here while budgets are set
   std::vector<int> base;          // [G] simulations already through each root: kept_visits - 1 after an advance, else 0
   bool selected = false;          // a selection has been issued since the last begin / advance
+  // ---- live-row numbering (fpc_search_set_live_rows)
+  bool live_rows = false;         // the setting; every selection latches it into t.inv (number_live_rows)
+  int *d_live = nullptr;          // [4][max_games] live_row | inv | c_slot | c_turn, then n_live; allocated when first switched on
+  int live_n = 0;                 // step entry points: the live rows of the pending selection
   // ---- device-side move choice (fpc_search_play); allocated on the first call
   double *d_powtab = nullptr;     // [max_sims + 16] pow(v, 1 / powtab_T) by the host libm
   double powtab_T = -1.0;         // temperature the uploaded table was made for (-1: none yet)
@@ -627,29 +631,52 @@ static void launch_expand(fpc_engine *e, const LogitSrc &src, const float *stats
   e->pending_vl = fuse && e->multi;
 }
 
-// softmax chunk statistics of logits that did not come from the internal policy Linear (one record set per row)
+// softmax chunk statistics of logits that did not come from the internal policy Linear (one record set per row; under
+// the live-row numbering the caller's buffers hold the n_live live rows only)
 static void launch_partials(fpc_engine *e, const float *logits_dev) {
-  const int nchunks = (e->dc.A / 4 + SM_THREADS - 1) / SM_THREADS, rows = e->rows_k * e->G;
+  const int nchunks = (e->dc.A / 4 + SM_THREADS - 1) / SM_THREADS, rows = e->t.inv ? e->live_n : e->rows_k * e->G;
+  if (rows == 0) return;
   FPC_LAUNCH(k_softmax_partials, rows * nchunks, SM_THREADS, e->stream, logits_dev, e->dc.A, rows, nchunks, e->d_stats);
 }
 
 // the leaf-parallel kernels leave the GLOBAL pool index g*board_cap + slot in leaf_slot: the encoders read it with stride 0
 static int leaf_board_stride(const fpc_engine *e) { return e->pending_vl ? 0 : e->t.board_cap; }
 
+// fpc_search_set_live_rows: the four arrays of k_live_rows (live_row | inv | c_slot | c_turn) and its count
+static int *live_array(const fpc_engine *e, int i) { return e->d_live + (size_t)i * e->cfg.max_games; }
+static int *live_count(const fpc_engine *e) { return live_array(e, 4); }
+
+// After EVERY selection: with the switch on, its live rows are numbered (k_live_rows) and the numbering is latched into
+// t.inv, which the expansion of that selection reads; with it off t.inv is null and nothing is launched.
+static void number_live_rows(fpc_engine *e) {
+  if (!e->live_rows) { e->t.inv = nullptr; return; }
+  FPC_LAUNCH(k_live_rows, 1, LIVE_THREADS, e->stream, (const int *)e->t.leaf_node, (const int *)e->t.leaf_slot, (const int *)e->t.leaf_turn,
+             e->rows_k * e->G, e->G, leaf_board_stride(e), live_array(e, 0), live_array(e, 1), live_array(e, 2), live_array(e, 3), live_count(e));
+  e->t.inv = live_array(e, 1);
+}
+
 // the step entry points: the pending leaves encoded in f32 for the external evaluator, and how many are live
 static int finish_select(fpc_engine *e, int *n_live, const float **enc_dev) {
   const int rows = e->rows_k * e->G;
-  FPC_LAUNCH(k_encode, rows, 64, e->stream, e->dc, (const fpc_board *)e->t.boards, leaf_board_stride(e),
-             (const int *)e->t.leaf_slot, (const int *)e->t.leaf_turn, rows, 0, e->d_enc_f32, (uint16_t *)nullptr,
-             (uint16_t)0, -1);
+  number_live_rows(e);
+  const bool compact = e->t.inv != nullptr;     // rows 0..n_live-1 hold the live leaves in ascending row order, the rest are zero
+  FPC_LAUNCH(k_encode, rows, 64, e->stream, e->dc, (const fpc_board *)e->t.boards, compact ? 0 : leaf_board_stride(e),
+             (const int *)(compact ? live_array(e, 2) : e->t.leaf_slot), (const int *)(compact ? live_array(e, 3) : e->t.leaf_turn), rows, 0,
+             e->d_enc_f32, (uint16_t *)nullptr, (uint16_t)0, -1);
   HIPCHK(e, hipGetLastError());
   mark(e, 1);
   e->stats.launches_select++;
-  std::vector<int> slots(rows);
-  HIPCHK(e, hipMemcpyAsync(slots.data(), e->t.leaf_slot, (size_t)rows * sizeof(int), hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(e, hipStreamSynchronize(e->stream));
   int live = 0;
-  for (int s : slots) live += s >= 0;
+  if (compact) {
+    HIPCHK(e, hipMemcpyAsync(&live, live_count(e), sizeof(int), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    e->live_n = live;
+  } else {
+    std::vector<int> slots(rows);
+    HIPCHK(e, hipMemcpyAsync(slots.data(), e->t.leaf_slot, (size_t)rows * sizeof(int), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    for (int s : slots) live += s >= 0;
+  }
   if (n_live) *n_live = live;
   if (enc_dev) *enc_dev = e->d_enc_f32;
   return 0;
@@ -744,15 +771,34 @@ int fpc_search_set_leaves(fpc_engine *e, int leaves, double virtual_loss) {
   return 0;
 }
 
+int fpc_search_set_live_rows(fpc_engine *e, int on) {
+  if (!e) return fail(e, FPC_EINVAL, "null engine");
+  if (on < 0 || on > 1) return fail(e, FPC_EINVAL, "fpc_search_set_live_rows: on = %d outside 0..1", on);
+  if (e->searching && e->selected && e->stepping)
+    return fail(e, FPC_ESTATE, "fpc_search_set_live_rows: a selection has been issued and the search's results have not been read");
+  USE_DEV(e);
+  int r;
+  if (on && !e->d_live && (r = dalloc(e, &e->d_live, (size_t)4 * e->cfg.max_games + 1))) return r;
+  e->live_rows = on != 0;
+  return 0;
+}
+
 #ifndef FPC_EMUL
-// the pending leaves as the network's input: the tower megakernels encode them themselves, the other paths take k_encode's
+// the pending leaves as the network's input: the tower megakernels encode them themselves, the other paths take k_encode's.
+// Under the live-row numbering the network's row j is the j-th live leaf (k_live_rows' c_slot / c_turn, global pool
+// indices: stride 0), rows n_live.. are dead, and beyond one 256-row tile the policy Linear skips the tiles without a
+// live row (single-tile shapes pass no count: they run exactly the kernels of the switch off).
 static void stage_leaves(fpc_engine *e) {
   const int rows = e->rows_k * e->G;
+  const bool compact = e->t.inv != nullptr;
+  const int stride = compact ? 0 : leaf_board_stride(e);
+  const int *slot = compact ? live_array(e, 2) : e->t.leaf_slot, *turn = compact ? live_array(e, 3) : e->t.leaf_turn;
+  e->nn.set_live_count(compact && rows > 256 ? live_count(e) : nullptr);
   if (e->nn.takes_boards())
-    e->nn.set_board_input((const fpc_board *)e->t.boards, leaf_board_stride(e), (const int *)e->t.leaf_slot, (const int *)e->t.leaf_turn);
+    e->nn.set_board_input((const fpc_board *)e->t.boards, stride, slot, turn);
   else
-    FPC_LAUNCH(k_encode, rows, 64, e->stream, e->dc, (const fpc_board *)e->t.boards, leaf_board_stride(e), (const int *)e->t.leaf_slot,
-               (const int *)e->t.leaf_turn, rows, 1, (float *)nullptr, e->nn.input16(), e->nn.one16(), -1);
+    FPC_LAUNCH(k_encode, rows, 64, e->stream, e->dc, (const fpc_board *)e->t.boards, stride, slot, turn, rows, 1, (float *)nullptr,
+               e->nn.input16(), e->nn.one16(), -1);
 }
 #endif
 
@@ -775,6 +821,7 @@ int fpc_search_run(fpc_engine *e, int sims) {
   for (int s = 0; s < steps; ++s) {
     mark(e, 0);
     if (s == 0) launch_select(e, leaves_of(0));
+    number_live_rows(e);
     stage_leaves(e);
     mark(e, 1);
     e->nn.mark_fn = [](void *ctx, int tag) { mark((fpc_engine *)ctx, tag); };

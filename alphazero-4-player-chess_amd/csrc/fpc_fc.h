@@ -39,6 +39,13 @@ struct FcArgs {
   float *part;            // [slabs][Mtot][256]
   int Kp, Np, ksteps, Mtot;
   int G1, s1, s2;         // groups [0,G1): s1 splits; groups [G1, Np/256): s2 splits
+  // live-row numbering (fpc_search_set_live_rows; null: off, or a single row tile): rows *n_live.. of X are dead, and a
+  // block whose 256-row tile holds none of the live ones returns before it touches memory -- the weights are streamed
+  // ceil(*n_live / 256) times, not once per tile of the batch.  The dead tiles' slabs keep what they held; nobody reads them.
+  // The host launches the LIVE instantiation of the kernels only with a non-null pointer: behind a null TEST the compiler
+  // holds every other kernel-argument load back until the pointer has arrived (a second scalar round trip at the head of
+  // every block), so the null case is a kernel of its own whose instruction stream is the one it was before.
+  const int *n_live;
 };
 
 constexpr int FC_THREADS = 256;
@@ -85,9 +92,10 @@ __device__ __forceinline__ void fc_dma_nt(const void *gsrc_uniform, uint32_t lan
 //     first k-step of a stage: the weights of its second k-step were issued three k-steps ago; behind their last
 //     piece came 1 + 8 + 8 pieces -> vmcnt(17); second k-step: the activations of the next stage (last piece: two
 //     k-steps ago) and everything older -> vmcnt(8), then THE stage barrier.
-template <int DT>
+template <int DT, bool LIVE = false>
 __global__ void __launch_bounds__(FC_THREADS, 1) k_fc16(FcArgs g) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];   // [3 X buffers][4 per-wave weight rings]
+  if (LIVE && (int)blockIdx.y * 256 >= *g.n_live) return;    // block-uniform: a tile without a live row
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int nbig = g.G1 * g.s1;
@@ -251,9 +259,10 @@ constexpr int FCW_COLS = 384;
 constexpr int FCW_WRING = 24 * 1024;
 constexpr int FCW_LDS = 2 * FC_XBUF + 4 * FCW_WRING;   // 163840
 
-template <int DT>
+template <int DT, bool LIVE = false>
 __global__ void __launch_bounds__(FC_THREADS, 1) k_fcw(FcArgs g) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];   // [2 X buffers][4 per-wave weight rings]
+  if (LIVE && (int)blockIdx.y * 256 >= *g.n_live) return;    // block-uniform: a tile without a live row
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int sk = g.s1;                            // K-splits per column group (every group alike)
@@ -385,12 +394,14 @@ __global__ void __launch_bounds__(FC_THREADS, 1) k_fcw(FcArgs g) {
 // Sums a column group's K-split slabs and the bias in fixed order, writes the logits, and -- while the
 // block still holds its 1024 logits of the row in registers -- leaves that chunk's softmax statistics
 // (softmax_chunk_stats, fpc_tree_kernels.h) for the expansion, which then never sweeps the row again.
+// LIVE (n_live non-null, FcArgs): the rows at or beyond *n_live are dead -- their blocks return at once, their records stay.
+template <bool LIVE = false>
 __global__ void __launch_bounds__(256) k_fc_reduce(const float *part, const float *bias, int G1, int s1, int s2, int gw, int Mtot, int A,
-                                                   int n_rows, float *logits, float *stats) {
+                                                   int n_rows, const int *n_live, float *logits, float *stats) {
   __shared__ float red[8];
   const int q = blockIdx.x * 256 + threadIdx.x;         // float4 index within a row
   const int m = blockIdx.y;
-  if (m >= n_rows) return;
+  if (m >= n_rows || (LIVE && m >= *n_live)) return;
   const bool valid = q * 4 < A;
   float4 v{0.f, 0.f, 0.f, 0.f};
   if (valid) {

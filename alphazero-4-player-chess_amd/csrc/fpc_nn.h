@@ -325,8 +325,9 @@ __global__ void __launch_bounds__(GEMV_THREADS) k_policy_gemv(DevCfg c, Tree t, 
     while (cum[g + 1] <= p) ++g;                   // skip games without pairs
     const int pend = cum[g + 1] < p1 ? cum[g + 1] : p1;
     __syncthreads();                               // the previous game's row is no longer being read
+    const int xrow_g = t.inv != nullptr ? t.inv[g] : g;    // live-row numbering: the tower left this leaf's activations there (g owns pairs: live)
     for (int q = tid; q < chunks; q += GEMV_THREADS)
-      reinterpret_cast<u32x4_t *>(xs)[q] = *reinterpret_cast<const u32x4_t *>(X + (long)g * Kp + (long)q * 8);
+      reinterpret_cast<u32x4_t *>(xs)[q] = *reinterpret_cast<const u32x4_t *>(X + (long)xrow_g * Kp + (long)q * 8);
     __syncthreads();
     const uint16_t *legal = t.legal + (size_t)g * FPC_MAX_MOVES;
     for (int pp = p + wave; pp < pend; pp += GEMV_THREADS / 64) {
@@ -479,6 +480,11 @@ struct NN {
   int in_board_stride = 0;
   bool takes_boards() const { return use_tower || use_towerw; }
   void set_board_input(const fpc_board *b, int stride, const int *slot, const int *turn) { in_boards = b; in_board_stride = stride; in_leaf_slot = slot; in_leaf_turn = turn; }
+  // live-row numbering (fpc_search_set_live_rows): the device count of the next forward's live rows, which are its rows
+  // 0..count-1 -- the policy Linear skips the 256-row tiles at or beyond it.  Null (the default; cleared by the forward):
+  // every tile is computed.
+  const int *in_live_count = nullptr;
+  void set_live_count(const int *n_live) { in_live_count = n_live; }
   uint16_t one16() const { return dtype ? 0x3C00 : 0x3F80; }
   float *logits() { return d_logits; }
   float *stats() { return d_stats; }
@@ -704,6 +710,8 @@ struct NN {
   template <int DT>
   int forward_t(int n, float *logits_out, float *value_out, std::string *err) {
     int rc;
+    const int *const in_live_count = this->in_live_count;     // this forward's; the next one starts without
+    this->in_live_count = nullptr;
     const int M = ((n * PP + CONV_BM - 1) / CONV_BM) * CONV_BM;
     auto conv = [&](const ConvW &cw, const uint16_t *in, int in_ld, const uint16_t *res, uint16_t *out, int out_ld, int n_valid, int mode) -> int {
       ConvArgs g{};
@@ -824,18 +832,30 @@ struct NN {
       FcArgs f{};
       f.X = xfc; f.Wf = fcw; f.part = fc_part; f.Kp = Kp; f.Np = Np; f.ksteps = Kp / 16; f.Mtot = Gpad;
       f.G1 = fc_G1; f.s1 = fc_s1; f.s2 = fc_s2;
+      f.n_live = in_live_count;
       const int mtiles = (n + 255) / 256;
       const int blocks = fc_G1 * fc_s1 + (Np / fc_gw - fc_G1) * fc_s2;
       bool &fattr = attr_fc[DT];
       if (!fattr) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_fc16<DT>), hipFuncAttributeMaxDynamicSharedMemorySize, FC_LDS);
         (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_fcw<DT>), hipFuncAttributeMaxDynamicSharedMemorySize, FCW_LDS);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_fc16<DT, true>), hipFuncAttributeMaxDynamicSharedMemorySize, FC_LDS);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_fcw<DT, true>), hipFuncAttributeMaxDynamicSharedMemorySize, FCW_LDS);
         fattr = true;
       }
-      if (fc_layout == 2) hipLaunchKernelGGL((k_fcw<DT>), dim3(blocks, mtiles), dim3(FC_THREADS), FCW_LDS, stream, f);
+      // the LIVE instantiations (row tiles and rows at or beyond *n_live return at once) only with a count: fpc_fc.h, FcArgs
+      const bool live = in_live_count != nullptr;
+      if (fc_layout == 2 && live) hipLaunchKernelGGL((k_fcw<DT, true>), dim3(blocks, mtiles), dim3(FC_THREADS), FCW_LDS, stream, f);
+      else if (fc_layout == 2) hipLaunchKernelGGL((k_fcw<DT>), dim3(blocks, mtiles), dim3(FC_THREADS), FCW_LDS, stream, f);
+      else if (live) hipLaunchKernelGGL((k_fc16<DT, true>), dim3(blocks, mtiles), dim3(FC_THREADS), FC_LDS, stream, f);
       else hipLaunchKernelGGL((k_fc16<DT>), dim3(blocks, mtiles), dim3(FC_THREADS), FC_LDS, stream, f);
-      hipLaunchKernelGGL(k_fc_reduce, dim3((dc.A / 4 + 255) / 256, n), dim3(256), 0, stream, (const float *)fc_part, (const float *)fcb,
-                         fc_G1, fc_s1, fc_s2, fc_gw, Gpad, dc.A, n, skip_dense ? (float *)nullptr : logits_out, d_stats);
+      float *const dense_out = skip_dense ? (float *)nullptr : logits_out;
+      if (live)
+        hipLaunchKernelGGL(k_fc_reduce<true>, dim3((dc.A / 4 + 255) / 256, n), dim3(256), 0, stream, (const float *)fc_part, (const float *)fcb,
+                           fc_G1, fc_s1, fc_s2, fc_gw, Gpad, dc.A, n, in_live_count, dense_out, d_stats);
+      else
+        hipLaunchKernelGGL(k_fc_reduce<false>, dim3((dc.A / 4 + 255) / 256, n), dim3(256), 0, stream, (const float *)fc_part, (const float *)fcb,
+                           fc_G1, fc_s1, fc_s2, fc_gw, Gpad, dc.A, n, in_live_count, dense_out, d_stats);
       const hipError_t le = hipGetLastError();
       if (le != hipSuccess) { *err = std::string("k_fc launch failed: ") + hipGetErrorString(le); return FPC_ENODEVICE; }
     }

@@ -79,6 +79,9 @@ struct Tree {
   float noise_eps;
   // per-game simulation budgets (fpc_search_set_budget; null: none): [G] caps on sims_done, read by select_game only
   const int *budget;
+  // live-row numbering of the pending selection (fpc_search_set_live_rows, k_live_rows; null: off): [rows] the network row
+  // of step row r, -1 for a dead row.  Read by the expansion and k_policy_gemv only.
+  const int *inv;
 };
 
 // ---- LDS image of one wave --------------------------------------------------------------------
@@ -1669,6 +1672,57 @@ __global__ void __launch_bounds__(64) k_vl_roots(int *VL, int node_cap, int G) {
 }
 
 // ================================================================================================
+// k_live_rows (fpc_search_set_live_rows, opt-in): the live rows of the pending selection numbered densely in ascending
+// row order, so that everything between selection and expansion works on n_live rows instead of `rows`.
+//   live_row[j] = r, inv[r] = j for the j-th live row r (leaf_node[r] >= 0); inv[r] = -1 for a dead row;
+//   c_slot[j] = the GLOBAL board-pool index of row r's leaf state, c_turn[j] = its side to move: what the encoders read
+//   with board stride 0; c_slot[j] = -1, c_turn[j] = 0 for n_live <= j < rows (the tower's and k_encode's dead rows);
+//   *n_live = the count.
+// slot_stride: 0 when leaf_slot already holds the global index (a leaf-parallel selection), else board_cap (a one-leaf
+// selection stores the slot within game r % G's pool).
+// ONE block of LIVE_THREADS, chunks of LIVE_THREADS rows: every wave ballots its 64 rows, a lane's place is the popcount
+// of the lower lanes + the lower waves' counts of the chunk (LDS) + the offset carried over from the chunks before.  No
+// atomics: the numbering is a function of leaf_node alone.
+// ================================================================================================
+constexpr int LIVE_THREADS = 256;
+__global__ void __launch_bounds__(LIVE_THREADS) k_live_rows(const int *leaf_node, const int *leaf_slot, const int *leaf_turn, int rows,
+                                                            int G, int slot_stride, int *live_row, int *inv, int *c_slot, int *c_turn,
+                                                            int *n_live) {
+  __shared__ int wcount[2][LIVE_THREADS / 64];      // per chunk parity: one barrier per chunk is enough
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  int carried = 0;
+  for (int base = 0, par = 0; base < rows; base += LIVE_THREADS, par ^= 1) {
+    const int r = base + tid;
+    const bool in = r < rows;
+    const int node = in ? leaf_node[r] : -1;
+    const int slot = in ? leaf_slot[r] : -1;
+    const int turn = in ? leaf_turn[r] : 0;
+    const bool live = node >= 0;
+    const unsigned long long bal = __ballot(live);
+    if (lane == 0) wcount[par][wave] = __popcll(bal);
+    __syncthreads();
+    int below = 0, total = 0;
+    for (int w = 0; w < LIVE_THREADS / 64; ++w) {
+      const int cw = wcount[par][w];
+      below += w < wave ? cw : 0;
+      total += cw;
+    }
+    if (live) {
+      const int j = carried + below + __popcll(bal & ((1ull << lane) - 1ull));
+      live_row[j] = r;
+      inv[r] = j;
+      c_slot[j] = (r % G) * slot_stride + slot;
+      c_turn[j] = turn;
+    } else if (in) {
+      inv[r] = -1;
+    }
+    carried += total;
+  }
+  for (int j = carried + tid; j < rows; j += LIVE_THREADS) { c_slot[j] = -1; c_turn[j] = 0; }
+  if (tid == 0) *n_live = carried;
+}
+
+// ================================================================================================
 // deterministic f32 exp shared (as a numeric SPEC, DESIGN.md "fpc_expf") with the test oracle:
 // k = rint(x*log2e); r = x - k*ln2 (two fma steps); degree-7 Horner in fma; scale by 2^k.
 // ================================================================================================
@@ -1705,14 +1759,19 @@ __device__ __forceinline__ float fdiv_rn(float a, float b) {
 // Shared end of both expand kernels (one wave): s.pri[0..nl) = unnormalised legal probabilities in
 // ascending flat order, s.lsorted the flat indices.  Legal mass (sequential ascending f32 sum),
 // policy error, BackpropagateNodes (mcts.py:78) before ExpandNodes (mcts.py:79), children appended.
+// Where the network left a step row's outputs (value, softmax records, logits): at the row itself, or, under the
+// live-row numbering (t.inv, k_live_rows), at inv[row] -- one dependent load, requested with the up-front batch, on which
+// only the addresses of those outputs wait.  A dead row gets -1 there and must not use it as an index.
+__device__ __forceinline__ int live_net_row(const Tree &t, int row) { return t.inv != nullptr ? t.inv[row] : row; }
 struct ExpandPre {     // what expand_game / expand_legal_game fetch up front for expand_finish (one round trip with their own loads)
   float v;             // value[g]
   int path_len, path_node, nnodes;
 };
-__device__ __forceinline__ ExpandPre expand_prefetch(const Tree &t, int g, int row, const float *value) {
+// crow: the row of the network's outputs that holds this leaf (live_net_row; < 0: a dead row under the live-row numbering)
+__device__ __forceinline__ ExpandPre expand_prefetch(const Tree &t, int g, int row, int crow, const float *value) {
   ExpandPre e;
   const int lane = lane_id();
-  e.v = value[row];
+  e.v = crow >= 0 ? value[crow] : 0.f;
   e.path_len = t.path_len[row];
   e.path_node = lane < t.path_cap ? t.path[(size_t)row * t.path_cap + lane] : 0;
   e.nnodes = t.nnodes[g];
@@ -1885,11 +1944,11 @@ __device__ inline bool expand_game(WaveLds &s, const DevCfg &c, const Tree &t, i
   const int lane = lane_id();
   const size_t nb = (size_t)g * t.node_cap;
   const int nchunks = (c.A / 4 + SM_THREADS - 1) / SM_THREADS;     // A = (8R+8)*R*R is a multiple of 4 for even R
-  const float *st = stats + (size_t)row * SM_MAXCH * SM_REC;
   const uint16_t *legal = t.legal + (size_t)row * FPC_MAX_MOVES;
   // ONE round trip for everything whose address depends on no other load (a lone wave per CU pays the full memory
   // latency per dependent load): the leaf, its legal list (first 64 entries), the chunk records, the leaf turns of the
   // first 64 games (the batch's first live leaf is almost always among them), value / path / node count.
+  const int crow = live_net_row(t, row);
   const int n = t.leaf_node[row];
   const int nl = t.nlegal[row];
   const int own_turn = t.leaf_turn[row];
@@ -1898,8 +1957,9 @@ __device__ inline bool expand_game(WaveLds &s, const DevCfg &c, const Tree &t, i
   const int fl0 = legal[lane];                                    // lane < 64 <= FPC_MAX_MOVES: always in bounds
   float mc = -__builtin_inff(), sc = 0.f;
   bool nan = false;
-  if (lane < nchunks) { mc = st[lane * SM_REC]; sc = st[lane * SM_REC + 1]; nan = st[lane * SM_REC + 2] != 0.f; }
-  const ExpandPre pre = expand_prefetch(t, g, row, value);
+  const float *st = stats + (size_t)(crow >= 0 ? crow : 0) * SM_MAXCH * SM_REC;
+  if (lane < nchunks && crow >= 0) { mc = st[lane * SM_REC]; sc = st[lane * SM_REC + 1]; nan = st[lane * SM_REC + 2] != 0.f; }
+  const ExpandPre pre = expand_prefetch(t, g, row, crow, value);
   int turn0;
   if (c.rules & FPC_RULES_ROTATION) turn0 = own_turn;
   else {                                                          // the batch's FIRST live leaf (Q6)
@@ -1920,7 +1980,7 @@ __device__ inline bool expand_game(WaveLds &s, const DevCfg &c, const Tree &t, i
     const int fl = j < 64 ? fl0 : (int)legal[j];
     const int plane = fl / c.RR, pos = fl % c.RR;
     const int src = plane * c.RR + rot90_src(c.R, -turn0, pos / c.R, pos % c.R);
-    s.pri[j] = fpc_expf(logit_at(logits, row, c.A, src) - m) * inv;
+    s.pri[j] = fpc_expf(logit_at(logits, crow, c.A, src) - m) * inv;
     s.lsorted[j] = (uint16_t)fl;
   }
   __syncthreads();
@@ -1966,7 +2026,7 @@ template <bool MULTI>
 __device__ inline bool expand_legal_game(WaveLds &s, const DevCfg &c, const Tree &t, int g, int row, const float *ll, const float *value, int *VL) {
   const int lane = lane_id();
   const int n = t.leaf_node[row];
-  const ExpandPre pre = expand_prefetch(t, g, row, value);
+  const ExpandPre pre = expand_prefetch(t, g, row, live_net_row(t, row), value);
   if (n < 0) return true;
   const size_t nb = (size_t)g * t.node_cap;
   const int nl = t.nlegal[row];

@@ -159,6 +159,7 @@ _SIGS = {
     "fpc_set_rules": (C.c_int, [C.c_void_p, C.c_int]),
     "fpc_search_set_root_noise": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_float]),
     "fpc_search_set_leaves": (C.c_int, [C.c_void_p, C.c_int, C.c_double]),
+    "fpc_search_set_live_rows": (C.c_int, [C.c_void_p, C.c_int]),
     "fpc_tuples_reserve": (C.c_int, [C.c_void_p, C.c_int]),
     "fpc_tuples_reset": (C.c_int, [C.c_void_p]),
     "fpc_collect_tuples": (C.c_int, [C.c_void_p, P(C.c_int), C.c_int]),
@@ -615,6 +616,12 @@ class Engine:
         """leaf-parallel search (include/fpc_engine.h fpc_search_set_leaves): up to k leaves per game per simulation
         step, kept apart by virtual loss; the step-wise evaluator then sees [k*G, 24, R, R].  k = 1: one leaf per game."""
         self._chk(self.L.fpc_search_set_leaves(self.h, int(k), float(virtual_loss)))
+
+    def set_live_rows(self, on):
+        """live-row numbering (include/fpc_engine.h fpc_search_set_live_rows): every step's live leaves are the network's
+        rows 0..n_live-1 in ascending row order; the step-wise evaluator's encodings are in that order (rows n_live.. are
+        zero) and its logits / values are read at n_live rows only.  Same search results; persistent."""
+        self._chk(self.L.fpc_search_set_live_rows(self.h, int(on)))
 
     def set_root_noise(self, gamma, eps):
         """gamma: float32 array [n_games, MAX_MOVES] of Gamma(alpha) draws (None: off)"""

@@ -22,6 +22,10 @@ Per-game simulation budgets (opt-in, not reference semantics; include/fpc_engine
 args["sim_budget"] = "per_game" | "visit_target" makes continue_search give every game its own simulation count
 (budgets_for) instead of the batch-wide one; search(games, budgets=...) / continue_search(..., budgets=...) take an
 explicit per-game list.  Absent / None: no budget is ever set.
+
+Live-row numbering (opt-in; include/fpc_engine.h fpc_search_set_live_rows): args["live_rows"] = True makes every step work
+on its live leaves only -- the same trees; the fused search's policy Linear computes ceil(live / 256) row tiles, and an
+external evaluator sees [n_live,24,R,R] (the live leaves in ascending row order) and returns n_live rows.
 """
 import math
 
@@ -101,6 +105,8 @@ class MCTS:
         self.sim_budget = args.get("sim_budget", None) if hasattr(args, "get") else None
         if self.sim_budget not in SIM_BUDGET_MODES:
             raise ValueError("sim_budget must be one of %r, not %r" % (SIM_BUDGET_MODES, self.sim_budget))
+        # args["live_rows"] = True (opt-in): only the live leaves of a step are evaluated (fpc_search_set_live_rows)
+        self.live_rows = bool(args.get("live_rows", False)) if hasattr(args, "get") else False
 
     def engine_rows(self, G):
         """rows of the engine handle a search of G games needs (G * leaves_per_step)"""
@@ -145,6 +151,7 @@ class MCTS:
         else:
             eng.set_root_noise(None, 0.0)
         eng.search_begin(pods, float(self.args["C"]))
+        eng.set_live_rows(self.live_rows)                  # as set_leaves; here, where no selection can be pending
         if budgets is not None:
             budgets = [int(b) for b in budgets]
             eng.search_set_budget(budgets)
@@ -196,6 +203,7 @@ class MCTS:
             kept = eng.search_advance_refill(flats, keep_idx, fresh=pods, roots=pods)
         else:
             kept = eng.search_advance(flats, keep_idx, roots=pods)
+        eng.set_live_rows(self.live_rows)
         if budgets is None:
             budgets = budgets_for(kept, int(self.args["num_searches"]), eng.max_sims, self.sim_budget)
         if budgets is not None:
@@ -242,6 +250,8 @@ class MCTS:
                     n_live, enc_ptr = eng.search_select()
                     rows = G * leaves_of(i + 1)
                 continue
+            if self.live_rows:                         # the live leaves lead the batch, in ascending row order
+                rows = n_live
             if host_engine:
                 import ctypes
                 import numpy as np

@@ -275,6 +275,27 @@ int fpc_search_advance_refill(fpc_engine *e, const int *src_game /* nullable */,
  * n_games != the search's game count, a negative entry. */
 int fpc_search_set_budget(fpc_engine *e, const int *budget /* host [n_games], nullable */, int n_games);
 
+/* ---- live-row numbering (opt-in; additions only, fpc_abi_version() unchanged) -----------------------------------------
+ * Refill, budgets, FPC_RULES_TERMINAL and leaf-parallel collisions leave dead rows in a step, and with the switch off a
+ * dead row is evaluated like a live one.  With it on, every selection's live rows (leaf_node[r] >= 0, r = k*G + g) are
+ * numbered j = 0..n_live-1 IN ASCENDING r on the device (k_live_rows), and everything between the selection and the
+ * expansion works on that numbering: the network's row j is the j-th live leaf.  The trees are the same bit for bit --
+ * fpc_search_results, fpc_search_grandchildren, sims_done, alive and the error words do not change under any rule set,
+ * K, budget, reuse, refill, root noise or policy head: a row's network output is a function of that row's input and the
+ * weights alone, and under strict rules the batch-wide rotation (Q6) is that of the first live row, which is row 0 of
+ * the numbering.  Only where a leaf's row lies in the network batch changes.
+ *   fpc_search_run     the policy Linear computes ceil(n_live / 256) row tiles instead of ceil(rows / 256): a batch of
+ *                      more than 256 slots whose live leaves fit one tile streams the weights once.
+ *   step entry points  *n_live as before; enc_dev is [rows,24,R,R] with the live leaves in rows 0..n_live-1 (ascending
+ *                      r) and rows n_live.. all-zero; logits_dev / value_dev are read at rows 0..n_live-1 ONLY (buffers
+ *                      of n_live rows are enough).  With *n_live == 0 nothing needs evaluating, as before.
+ *   fpc_nn_forward     untouched.
+ * Persistent, like fpc_search_set_leaves; applies from the next selection.  May be called before fpc_search_begin, after
+ * fpc_search_begin / fpc_search_advance(_refill) and before that search's first selection, and on a finished search.
+ * FPC_ESTATE: a selection has been issued and the search's results have not been read (fpc_search_set_budget's rule).
+ * FPC_EINVAL: null engine, `on` outside 0..1.  The first call with on = 1 allocates 4 * max_games + 1 ints. */
+int fpc_search_set_live_rows(fpc_engine *e, int on);
+
 /* ---- device-side move choice (opt-in): what a self-play ply does between the finished search and fpc_search_advance /
  * the next fpc_search_begin -- choose each game's move from the root's visit counts (alphazero.py:104-118), make it
  * (TakeAction, :119) and judge the game (GetGameResult, :120-123) -- as ONE launch (k_play_ply, one wave per game); the
