@@ -48,6 +48,8 @@ class AlphaZero:
         self.model, self.optimizer, self.gameType, self.args = model, optimizer, gameType, args
         self.game_init_args = game_init_args
         self.scheduler = torch.optim.lr_scheduler.StepLR(optimizer, step_size=1000, gamma=0.1)   # alphazero.py:25-27
+        # args["fc_weights"] = "int8" (opt-in, fp16 engines): the self-play engine's policy Linear runs on int8 weights; MCTS reads
+        # the key and every weight sync (host export or device pack) carries it
         self.mcts = MCTS(gameType, evaluator if evaluator is not None else model, args)
         self.device_replay = bool(args.get("device_replay", False)) if hasattr(args, "get") else False
         if self.device_replay:

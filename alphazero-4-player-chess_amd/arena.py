@@ -18,6 +18,8 @@ Q6), pi = child visit counts (alphazero.py:104-110), TakeAction(Move(flat)) and 
     composition exactly as the reference's would (Q6).
   * Result of a game: GameResult WIN_RY / WIN_BG decide it, STALEMATE is a draw; a game still running
     after max_game_length plies is adjudicated by the sign of CalculateHeuristic for the side to move.
+  * The searches are the caller's: an MCTS built with args["fc_weights"] = "int8" plays its side on the int8 policy
+    Linear (mcts.py), so "int8 against w16 of the same weights" is a pairing like any other.
 """
 import numpy as np
 

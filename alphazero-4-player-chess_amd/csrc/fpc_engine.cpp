@@ -122,6 +122,9 @@ struct fpc_engine {
   int pack_tab_convs = 0;
   hipEvent_t pk_ev[2] = {nullptr, nullptr};   // around the pack kernels while fpc_set_timing is on
   float pack_ms = -1.f;
+  int fc_wtype = FPC_FC_W16;             // fpc_set_fc_weight_type: the policy Linear's weight type of the next pack
+  float *d_fc8_scale = nullptr;          // k_fc_rowmax's output: [fc8_scale_n] scales + one int (the non-finite flag)
+  int fc8_scale_n = 0;
   // ---- stats
   bool timing = false;
   int policy_mode = 0;            // FPC_POLICY_FULL / FPC_POLICY_LEGAL (fpc_search_run only)
@@ -1646,6 +1649,20 @@ int fpc_set_timing(fpc_engine *e, int enabled) {
   e->timing = enabled != 0;
   return 0;
 }
+int fpc_set_fc_weight_type(fpc_engine *e, int type) {
+  if (!e || (type != FPC_FC_W16 && type != FPC_FC_W8)) return fail(e, FPC_EINVAL, "fpc_set_fc_weight_type: type must be FPC_FC_W16 or FPC_FC_W8");
+  e->fc_wtype = type;
+  return 0;
+}
+const char *fpc_nn_fc_kernel(fpc_engine *e) {
+#ifdef FPC_EMUL
+  (void)e;
+  return "";
+#else
+  if (!e || !e->nn.loaded) return "";
+  return e->nn.fc_wtype ? "k_fcw8" : e->nn.fc_layout == 2 ? "k_fcw" : "k_fc16";
+#endif
+}
 const char *fpc_nn_kernel(fpc_engine *e) {
 #ifdef FPC_EMUL
   (void)e;
@@ -1696,9 +1713,10 @@ int pack_geom_from(fpc_engine *e, int hidden, int nblocks, int fc_layout, PackGe
   g->Kp = (A + 511) / 512 * 512;
   if (fc_layout == 0) fc_layout = pk_plan_fcw((A + PK_FCW_COLS - 1) / PK_FCW_COLS * PK_FCW_COLS, g->Kp, pack_cus()) ? 2 : 1;
   g->fc_layout = fc_layout;
+  g->fc_wtype = e->fc_wtype;
   const int gw = fc_layout == 2 ? PK_FCW_COLS : 256;
   g->Np = (A + gw - 1) / gw * gw;
-  return pk_check_geom(g->F, g->nblocks, g->Np, g->Kp, g->fc_layout, A, pack_cus(), &g->fcw_split, &e->err);
+  return pk_check_geom(g->F, g->nblocks, g->Np, g->Kp, g->fc_layout, g->fc_wtype, g->dtype, A, pack_cus(), &g->fcw_split, &e->err);
 }
 
 // convolution i of the descriptor in blob order: stem, c1[0], c2[0], ..., policy, value
@@ -1742,6 +1760,32 @@ int pack_ensure_tab(fpc_engine *e, int nconv) {
   return 0;
 }
 
+// int8 policy Linear, first pass (k_fc_rowmax): the row scales into the engine's scratch row and the non-finite flag to
+// the host.  Runs BEFORE anything is written to a blob or to the live network: a non-finite weight refuses the pack.
+int pack_fc8_scan(fpc_engine *e, const fpc_net_src *s, const PackGeom &g, const char *fn) {
+  if (!g.fc_wtype) return 0;
+  int r;
+  if (e->fc8_scale_n < g.Np) {
+    float *grown = nullptr;
+    if ((r = dalloc(e, &grown, (size_t)g.Np + 16))) return r;
+    if (e->d_fc8_scale) {
+      (void)hipFree(e->d_fc8_scale);
+      e->allocs.erase(std::find(e->allocs.begin(), e->allocs.end(), (void *)e->d_fc8_scale));
+    }
+    e->d_fc8_scale = grown;
+    e->fc8_scale_n = g.Np;
+  }
+  int *flag = reinterpret_cast<int *>(e->d_fc8_scale + g.Np);
+  int bad = 0;
+  HIPCHK(e, hipMemcpyAsync(flag, &bad, sizeof(int), hipMemcpyHostToDevice, e->stream));
+  FPC_LAUNCH(k_fc_rowmax, g.Np, PK_THREADS, e->stream, s->fc_w, g.A, e->d_fc8_scale, flag);
+  HIPCHK(e, hipGetLastError());
+  HIPCHK(e, hipMemcpyAsync(&bad, flag, sizeof(int), hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(e, hipStreamSynchronize(e->stream));
+  if (bad) return fail(e, FPC_EWEIGHTS, "%s: the policy Linear holds a non-finite weight: int8 export refused, nothing was written", fn);
+  return 0;
+}
+
 // launches the three pack kernels on the engine's stream (timed if fpc_set_timing is on); the caller synchronises
 int pack_launch(fpc_engine *e, const fpc_net_src *s, const PackGeom &g, const PackDst &d) {
   const int nconv = g.nconv();
@@ -1766,7 +1810,11 @@ int pack_launch(fpc_engine *e, const fpc_net_src *s, const PackGeom &g, const Pa
   const int bpc = std::min(64, (max_items + PK_THREADS - 1) / PK_THREADS);
   FPC_LAUNCH(k_pack_conv, nconv * bpc, PK_THREADS, e->stream, (const PackConv *)e->d_pack_tab, bpc, g.dtype);
   const int nchunks = (g.RR + PK_PC - 1) / PK_PC;
-  FPC_LAUNCH(k_pack_fc, (g.Np / 16) * nchunks, PK_THREADS, e->stream, s->fc_w, g.A, g.A_ch, g.RR, g.Np, g.Kp, g.dtype, d.fcw);
+  if (g.fc_wtype)       // the scales: pack_fc8_scan left them in the scratch row
+    FPC_LAUNCH(k_pack_fc8, (g.Np / PK_ROWS8) * nchunks, PK_THREADS, e->stream, s->fc_w, (const float *)e->d_fc8_scale, g.A, g.A_ch, g.RR, g.Np, g.Kp,
+               reinterpret_cast<unsigned char *>(d.fcw), d.fcs);
+  else
+    FPC_LAUNCH(k_pack_fc, (g.Np / 16) * nchunks, PK_THREADS, e->stream, s->fc_w, g.A, g.A_ch, g.RR, g.Np, g.Kp, g.dtype, d.fcw);
   const int mblk = std::min(64, (g.Np + g.RR * 32 + PK_THREADS) / PK_THREADS);
   FPC_LAUNCH(k_pack_misc, mblk, PK_THREADS, e->stream, s->fc_b, s->vfc_w, s->vfc_b, g.A, g.RR, g.Np, mblk, d.fcb, d.vw, d.vb);
   HIPCHK(e, hipGetLastError());
@@ -1803,15 +1851,17 @@ int fpc_weights_pack(fpc_engine *e, const fpc_net_src *src, int fc_layout, void 
   int r;
   if ((r = pack_geom(e, src, fc_layout, &g, "fpc_weights_pack"))) return r;
   std::vector<uint64_t> cw, cb;
-  uint64_t fcw, fcb, vw, vb;
-  const uint64_t total = pk_blob_layout(g, &cw, &cb, &fcw, &fcb, &vw, &vb);
+  uint64_t fcw, fcb, vw, vb, fcs;
+  const uint64_t total = pk_blob_layout(g, &cw, &cb, &fcw, &fcb, &vw, &vb, &fcs);
   if (cap < total) return fail(e, FPC_EINVAL, "fpc_weights_pack: the blob needs %llu bytes, cap is %llu", (unsigned long long)total, (unsigned long long)cap);
   unsigned char *base = (unsigned char *)blob_dev;
   PackDst d;
   for (size_t i = 0; i < cw.size(); ++i) { d.cw.push_back((uint16_t *)(base + cw[i])); d.cb.push_back((float *)(base + cb[i])); }
   d.fcw = (uint16_t *)(base + fcw); d.fcb = (float *)(base + fcb); d.vw = (float *)(base + vw); d.vb = (float *)(base + vb);
-  if ((r = pack_ensure_tab(e, g.nconv()))) return r;      // the last thing that can fail before something is enqueued
-  int32_t hdr[16] = {0, 3, g.R, g.F, g.nblocks, g.dtype, g.A_ch, g.Np, g.Kp, g.fc_layout, 0, 0, 0, 0, 0, 0};
+  d.fcs = g.fc_wtype ? (float *)(base + fcs) : nullptr;
+  if ((r = pack_ensure_tab(e, g.nconv()))) return r;
+  if ((r = pack_fc8_scan(e, src, g, "fpc_weights_pack"))) return r;      // the last thing that can fail before something is written
+  int32_t hdr[16] = {0, 3 + g.fc_wtype, g.R, g.F, g.nblocks, g.dtype, g.A_ch, g.Np, g.Kp, g.fc_layout, g.fc_wtype, 0, 0, 0, 0, 0};
   memcpy(hdr, "FPCW", 4);
   HIPCHK(e, hipMemcpyAsync(base, hdr, sizeof(hdr), hipMemcpyHostToDevice, e->stream));
   if ((r = pack_launch(e, src, g, d))) return r;
@@ -1832,11 +1882,12 @@ int fpc_load_weights_device(fpc_engine *e, const fpc_net_src *src, int fc_layout
 #else
   fpc::NN &nn = e->nn;
   if ((r = pack_ensure_tab(e, g.nconv()))) return r;
-  // same geometry: straight into the live allocations, nothing freed or allocated; else allocate as fpc_load_weights does
-  if (!nn.same_geom(g.F, g.nblocks, g.Np, g.Kp, g.fc_layout) && (r = nn.alloc_net(g.F, g.nblocks, g.Np, g.Kp, g.fc_layout, g.fcw_split, &e->err))) return r;
+  if ((r = pack_fc8_scan(e, src, g, "fpc_load_weights_device"))) return r;
+  // same geometry (the weight type included): straight into the live allocations, nothing freed or allocated; else allocate as fpc_load_weights does
+  if (!nn.same_geom(g.F, g.nblocks, g.Np, g.Kp, g.fc_layout, g.fc_wtype) && (r = nn.alloc_net(g.F, g.nblocks, g.Np, g.Kp, g.fc_layout, g.fc_wtype, g.fcw_split, &e->err))) return r;
   PackDst d;
   for (fpc::ConvW *cw : nn.convs_in_blob_order()) { d.cw.push_back(cw->w); d.cb.push_back(cw->b); }
-  d.fcw = nn.fcw; d.fcb = nn.fcb; d.vw = nn.vw;
+  d.fcw = nn.fcw; d.fcb = nn.fcb; d.vw = nn.vw; d.fcs = nn.fcs;
   d.vb = (float *)(e->d_pack_tab + (size_t)e->pack_tab_convs * sizeof(PackConv));
   nn.loaded = false;      // the live weights are about to be rewritten: a HIP failure on the way leaves no half-new network in use
   if ((r = pack_launch(e, src, g, d))) return r;

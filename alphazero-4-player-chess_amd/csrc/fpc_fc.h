@@ -390,6 +390,183 @@ __global__ void __launch_bounds__(FC_THREADS, 1) k_fcw(FcArgs g) {
 // destination registers ("+v" operands of the s_waitcnt statement), also for loads whose data nobody reads.
 // ------------------------------------------------------------------------------------------------------------
 
+// ------------------------------------------------------------------------------------------------------------
+// k_fcw8 (opt-in, blob version 4 / fc_wtype 1, fp16 operands): k_fcw with the weight stream in int8 -- half the bytes of
+// the one stream the kernel is bound by (0.55 GB instead of 1.11 GB at 14x14), everything behind the slabs unchanged.
+// Numbers: q = the exporter's int8 with one f32 scale s_n per output column; a block accumulates
+// X . fp16(q)^T over its K part in the MFMAs (the conversion is exact), multiplies every accumulator element ONCE by its
+// column's s_n in f32 and stores the slab where and how k_fcw does: slab_k = fl(s_n * acc_k); k_fc_reduce / logit_at add
+// bias + slabs as before.
+// Weight order in memory: FRAGMENT PAIRS [k-step of 32][column pair of 32][lane = 16 q + c][2 tiles][8] bytes -- one
+// 1-KiB LDS-DMA piece is 64 lanes x 16 B = the fragments of TWO column tiles, and a lane reads back exactly the 16 bytes
+// it stored (the property the private ring rests on).  A wave's six tiles of a k-step are three contiguous pieces
+// (ntile = group * 24 + wave * 6 is even).
+// Schedule: k_fcw's.  Two activation stages (64 KiB) + a 12 KiB ring per wave (2 stages x 2 k-steps x 3 pieces) =
+// 112 KiB of LDS; the 48 KiB this frees are NOT spent (a deeper ring only behind a same-box A/B).  Issue pattern per
+// stage and wave: k-step 0: 8 X pieces (tile rows 0..7), then 3 weight pieces (rows 8, 10, 12); k-step 1: 3 weight pieces
+// (rows 2, 6, 10).  Counted waits, derived as k_fcw's:
+//   start of k-step (s, 0): the weights of (s, 1), issued in (s - 2, 1); behind them stage s - 1: 8 + 3 + 3   -> vmcnt(14)
+//   start of k-step (s, 1): the weights of (s + 1, 0), issued in (s - 1, 0); behind them 3 + 8 + 3             -> vmcnt(14)
+//   k-step (s, 1) behind tile row 13: the activations of stage s + 1, issued in (s, 0); behind them 3 + 3      -> vmcnt(6),
+//   then the stage barrier, as in k_fcw.
+// All of these loads are LDS-DMA pieces: none has a destination register, so the lesson above (waits tied to the
+// registers of asm loads) has nothing to tie here; the plain statements with a memory clobber are k_fcw's.
+// Fragments: at the start of k-step j the three raw pieces of k-step j + 1 are read (one u32x4 per lane and tile pair)
+// and converted during tile rows 1, 3 and 5 of k-step j into the six fp16 fragments the MFMAs of k-step j + 1 take:
+// per 32-bit word of four bytes  x = w ^ 0x80808080 (q + 128 as an unsigned byte), two v_perm_b32 put each byte under a
+// 0x64 (fp16 0x64uu = 1024 + u), one v_pk_add_f16 per pair subtracts 1152 -- exact for all 256 bytes.  The MFMAs are
+// inline asm, which the compiler's hazard recogniser does not look into: no converted register is consumed sooner than
+// 60 MFMAs after the VALU instruction that wrote it.
+struct Fc8Args {
+  FcArgs f;               // Wf: the int8 weights in pair order
+  const float *scale;     // [Np]
+};
+
+constexpr int FCW8_WRING = 12 * 1024;
+constexpr int FCW8_LDS = 2 * FC_XBUF + 4 * FCW8_WRING;   // 114688
+
+// four int8 (one 32-bit word, two's complement) -> four fp16 in two words, element order kept
+__device__ __forceinline__ void fc8_cvt4(uint32_t w, uint32_t &lo, uint32_t &hi) {
+  typedef _Float16 h2_t __attribute__((ext_vector_type(2)));
+  const uint32_t x = w ^ 0x80808080u;
+  const h2_t bias = {(_Float16)-1152.f, (_Float16)-1152.f};
+  const h2_t a = __builtin_bit_cast(h2_t, __builtin_amdgcn_perm(0x64646464u, x, 0x04010400u)) + bias;
+  const h2_t b = __builtin_bit_cast(h2_t, __builtin_amdgcn_perm(0x64646464u, x, 0x04030402u)) + bias;
+  lo = __builtin_bit_cast(uint32_t, a);
+  hi = __builtin_bit_cast(uint32_t, b);
+}
+
+template <bool LIVE = false>
+__global__ void __launch_bounds__(FC_THREADS, 1) k_fcw8(Fc8Args g8) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];   // [2 X buffers][4 per-wave weight rings]
+  const FcArgs &g = g8.f;
+  if (LIVE && (int)blockIdx.y * 256 >= *g.n_live) return;    // block-uniform: a tile without a live row
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int sk = g.s1;
+  const int id = blockIdx.x;
+  const int group = id / sk, split = id % sk;
+  const int npair = group * 12 + wave * 3;        // this wave's three column pairs (six 16-column tiles)
+  const int KS = g.ksteps / sk;
+  const int ks0 = split * KS;
+  const int S = KS / 4;                           // stages of BK = 64
+  const long mrow0 = (long)blockIdx.y * 256;
+  const unsigned char *wbase = reinterpret_cast<const unsigned char *>(g.Wf) + ((long)(ks0 / 2) * (g.Np / 32) + npair) * 1024;
+  const long wk32 = (long)(g.Np / 32) * 1024;
+  const uint32_t wlane = (uint32_t)lane * 16u;
+  const unsigned char *xbase = reinterpret_cast<const unsigned char *>(g.X) + ((mrow0 + wave * 64) * g.Kp + (long)ks0 * 16) * 2;
+  const long xpiece = 8L * g.Kp * 2;
+  uint32_t xlane[2];
+#pragma unroll
+  for (int par = 0; par < 2; ++par) {
+    const int j = (lane & 7) ^ ((par * 4 + (lane >> 4)) & 7);
+    xlane[par] = (uint32_t)((lane >> 3) * g.Kp * 2 + j * 16);
+  }
+  const uint32_t lds_w = (uint32_t)(2 * FC_XBUF + wave * FCW8_WRING);
+  const unsigned char *wr = smem + 2 * FC_XBUF + wave * FCW8_WRING + lane * 16;
+
+  f32x4_t acc[16][6];
+  u32x4_t xr[4], wf[2][6], raw[3];
+  const std::integral_constant<int, 0> c0{};
+  const std::integral_constant<int, 1> c1{};
+
+  auto issue_x = [&](int s, int p) {              // piece p (8 rows) of activation stage s
+    const int sc = s < S ? s : S - 1;
+    fc_dma(xbase + (long)p * xpiece + (long)sc * 128, xlane[p & 1],
+           (uint32_t)__builtin_amdgcn_readfirstlane((s & 1) * FC_XBUF + (wave * 64 + p * 8) * 128));
+  };
+  auto issue_w = [&](int s, int j, int p) {        // column pair p of k32-step j of stage s
+    const int sc = s < S ? s : S - 1;
+    fc_dma_nt(wbase + (long)(2 * sc + j) * wk32 + p * 1024, wlane,
+              (uint32_t)__builtin_amdgcn_readfirstlane(lds_w + ((s & 1) * 6 + j * 3 + p) * 1024));
+  };
+  auto xfrag = [&](int slot, int t, const unsigned char *ab, int j) {
+    xr[slot] = *reinterpret_cast<const u32x4_t *>(ab + lds_off<64>(t * 16 + (lane & 15), j * 4 + (lane >> 4)));
+  };
+  auto wraw = [&](int s, int j) {
+#pragma unroll
+    for (int p = 0; p < 3; ++p) raw[p] = *reinterpret_cast<const u32x4_t *>(wr + ((s & 1) * 6 + j * 3 + p) * 1024);
+  };
+  auto wcvt = [&](int b, int p) {                  // raw pair p -> the fragments of tiles 2 p and 2 p + 1
+    uint32_t o[8];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) fc8_cvt4(raw[p][i], o[2 * i], o[2 * i + 1]);
+    wf[b][2 * p] = u32x4_t{o[0], o[1], o[2], o[3]};
+    wf[b][2 * p + 1] = u32x4_t{o[4], o[5], o[6], o[7]};
+  };
+  auto kstep = [&](auto j_c, auto z_c, int s) {
+    constexpr int J = decltype(j_c)::value;
+    constexpr bool Z = decltype(z_c)::value != 0;
+    constexpr int CUR = J, NXT = J ^ 1;
+    asm volatile("s_waitcnt vmcnt(14)" ::: "memory");
+    const unsigned char *ab = smem + (s & 1) * FC_XBUF;                                  // this stage's activations
+    const unsigned char *abn = J == 1 ? smem + ((s + 1) & 1) * FC_XBUF : ab;             // the next k-step's
+    __builtin_amdgcn_sched_barrier(0);
+    wraw(J == 1 ? s + 1 : s, NXT);
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int t = 0; t < 16; ++t) {
+#pragma unroll
+      for (int n = 0; n < 6; ++n) {
+        if (n < 4) fcw_mfma<1, true, Z>(acc[t][n], wf[CUR][n], xr[t & 3]);
+        else fcw_mfma<1, false, Z>(acc[t][n], wf[CUR][n], xr[t & 3]);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+      if (J == 1 && t == 13) { asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); __syncthreads(); }
+      if (t + 3 < 16) xfrag((t + 3) & 3, t + 3, ab, J);
+      else xfrag((t + 3) & 3, t + 3 - 16, abn, NXT);
+      if (t == 1 || t == 3 || t == 5) wcvt(NXT, (t - 1) / 2);
+      if (J == 0 && t < 8) issue_x(s + 1, t);
+      if (J == 0 && (t == 8 || t == 10 || t == 12)) issue_w(s + 2, 0, (t - 8) / 2);
+      if (J == 1 && (t == 2 || t == 6 || t == 10)) issue_w(s + 2, 1, (t - 2) / 4);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  };
+
+  // prologue: the activations of stage 0, the weights of stages 0 and 1, then the first fragments
+#pragma unroll
+  for (int p = 0; p < 8; ++p) issue_x(0, p);
+#pragma unroll
+  for (int st = 0; st < 2; ++st)
+#pragma unroll
+    for (int j = 0; j < 2; ++j) { issue_w(st, j, 0); issue_w(st, j, 1); issue_w(st, j, 2); }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+#pragma unroll
+  for (int t = 0; t < 3; ++t) xfrag(t, t, smem, 0);
+  wraw(0, 0);
+#pragma unroll
+  for (int p = 0; p < 3; ++p) wcvt(0, p);
+  // the converted fragments of (0, 0) come out of VALU instructions right here: the wait states between a VALU write and
+  // an MFMA read the compiler cannot count across the asm boundary
+  asm volatile("s_nop 7" ::: "memory");
+
+  kstep(c0, c1, 0);                               // (0, 0): C = 0
+  kstep(c1, c0, 0);
+#pragma unroll 1
+  for (int s = 1; s < S; ++s) {
+    kstep(c0, c0, s);
+    kstep(c1, c0, s);
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the clamped tail pieces: nothing may still target LDS at exit
+  // as in k_fcw: the wait states between an 8-pass MFMA writing a register and a v_accvgpr_read / VALU reading it
+  asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 3" ::: "memory");
+
+  // the lane's 24 scales: six tiles x four consecutive columns
+  f32x4_t sc[6];
+  const float *scl = g8.scale + (long)group * FCW_COLS + wave * 96 + (lane >> 4) * 4;
+#pragma unroll
+  for (int n = 0; n < 6; ++n) sc[n] = *reinterpret_cast<const f32x4_t *>(scl + n * 16);
+  float *out = g.part + ((long)id * g.Mtot + mrow0) * FCW_COLS;
+#pragma unroll
+  for (int t = 0; t < 16; ++t) {
+    const int m = t * 16 + (lane & 15);
+#pragma unroll
+    for (int n = 0; n < 6; ++n)
+      *reinterpret_cast<f32x4_t *>(out + (long)m * FCW_COLS + wave * 96 + n * 16 + (lane >> 4) * 4) = acc[t][n] * sc[n];
+  }
+}
+
 // logits[m][n] = bias[n] + slab[base][m][n%256] + slab[base+1][m][n%256] + ...   (fixed order)
 // Sums a column group's K-split slabs and the bias in fixed order, writes the logits, and -- while the
 // block still holds its 1024 logits of the row in registers -- leaves that chunk's softmax statistics

@@ -274,6 +274,24 @@ __global__ void __launch_bounds__(256) k_fc_unfrag(const uint16_t *Wf, uint16_t 
   *reinterpret_cast<u32x4_t *>(W2 + (long)n * Kp + (long)k8 * 8) = *reinterpret_cast<const u32x4_t *>(Wf + src);
 }
 
+// the same from int8 weights in fragment-PAIR order (blob version 4): W2 = fp16(q), exact; the scales stay with k_policy_gemv
+__global__ void __launch_bounds__(256) k_fc_unfrag8(const unsigned char *Wq, uint16_t *W2, int Np, int Kp) {
+  const long c = (long)blockIdx.x * 256 + threadIdx.x;
+  const long chunks = (long)Np * (Kp / 8);
+  if (c >= chunks) return;
+  const int n = (int)(c / (Kp / 8)), k8 = (int)(c % (Kp / 8));
+  // [k-step of 32][column pair of 32][lane = 16 q + c][2 tiles][8]
+  const long src = (((long)(k8 >> 2) * (Np / 32) + (n >> 5)) * 64 + ((k8 & 3) * 16 + (n & 15))) * 16 + ((n >> 4) & 1) * 8;
+  const u32x2_t b = *reinterpret_cast<const u32x2_t *>(Wq + src);
+  u32x4_t o;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const uint32_t w = b[i >> 1] >> ((i & 1) * 16);
+    o[i] = E16<1>::pack2((float)(int8_t)(w & 0xff), (float)(int8_t)((w >> 8) & 0xff));
+  }
+  *reinterpret_cast<u32x4_t *>(W2 + (long)n * Kp + (long)k8 * 8) = o;
+}
+
 template <int DT>
 struct Dot16;
 template <>
@@ -293,9 +311,11 @@ struct Dot16<1> {
 
 constexpr int GEMV_THREADS = 256, GEMV_MAXG = 2048;
 
-template <int DT>
+// W8 (int8 weights loaded: W2 holds fp16(q)): the dot product is scaled by the column's f32 scale before the bias is added;
+// the 16-bit variant never reads `scale`
+template <int DT, bool W8 = false>
 __global__ void __launch_bounds__(GEMV_THREADS) k_policy_gemv(DevCfg c, Tree t, int G, const uint16_t *X, const uint16_t *W2,
-                                                              const float *bias, int Kp, float *ll) {
+                                                              const float *bias, int Kp, float *ll, const float *scale) {
   extern __shared__ __attribute__((aligned(16))) unsigned char xs[];     // Kp * 2 bytes: one game's activation row
   __shared__ int cum[GEMV_MAXG + 1];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -354,7 +374,7 @@ __global__ void __launch_bounds__(GEMV_THREADS) k_policy_gemv(DevCfg c, Tree t, 
       }
       float a = (a0 + a1) + (a2 + a3);
       for (int off = 32; off >= 1; off >>= 1) a += __shfl_xor(a, off);
-      if (lane == 0) ll[(size_t)g * FPC_MAX_MOVES + j] = bias[nsrc] + a;
+      if (lane == 0) ll[(size_t)g * FPC_MAX_MOVES + j] = W8 ? bias[nsrc] + scale[nsrc] * a : bias[nsrc] + a;
     }
     p = pend;
   }
@@ -391,7 +411,7 @@ __global__ void __launch_bounds__(64) k_nchw_to_grid(const float *x, int n, int 
 
 // ------------------------------------------------------------------------------------------------
 // weight blob (written by alphazero-4-player-chess_amd/weights.py):
-//   header  : char magic[4]="FPCW"; int32 version (3; version 2 = the retired 32x32x16 fragment order of rounds 1-4: refused), R, F, nblocks, dtype, A_ch, Np, Kp, fc_layout; pad to 64 B
+//   header  : char magic[4]="FPCW"; int32 version (3, or 4 = int8 policy Linear, below; version 2 = the retired 32x32x16 fragment order of rounds 1-4: refused), R, F, nblocks, dtype, A_ch, Np, Kp, fc_layout; pad to 64 B
 //   sections, each 64-B aligned, in this order:
 //     stem   w16[9][Fp][32]     b f32[Fp]          (Fp = F rounded up to 128)
 //     block i: c1 w16[9][Fp][F] b f32[Fp] ; c2 w16[9][Fp][F] b f32[Fp]
@@ -399,12 +419,17 @@ __global__ void __launch_bounds__(64) k_nchw_to_grid(const float *x, int n, int 
 //     value  conv w16[9][128][F] b f32[128]  (both heads: Cout zero-padded to the 128-wide tile)
 //     policy fc   w16 in MFMA fragment order [Kp/32][Np/16][64 lanes][8] (lane = 16*(k/8%4) + n%16; Np = 256 * groups for fc_layout 1, 384 * groups for 2)   b f32[Np]
 //     value  fc   w f32[R*R][32] b f32[1]
+//   version 4 = header word fc_wtype 1 (byte 40; 0 in version 3, whose bytes are unchanged): the policy-fc section is
+//     int8 in fragment-PAIR order [Kp/32][Np/32][64 lanes = 16 q + c][2 tiles][8], element (ks, np, q, c, t, e) =
+//     q8[32 np + 16 t + c][32 ks + 8 q + e] (two's complement; the exporter never writes -128, a blob may), then
+//     scale f32[Np] (1.0 in the padding), then b f32[Np].  Only with fc_layout 2 and dtype 1 (fp16): k_fcw8.
 // ------------------------------------------------------------------------------------------------
 struct BlobHeader {
   char magic[4];
   int32_t version, R, F, nblocks, dtype, A_ch, Np, Kp;
   int32_t fc_layout;     // policy Linear: 1 = 16x16x32 fragments over 256-column groups (k_fc16), 2 = over 384-column groups (k_fcw); 0 (32x32x16, k_fc) retired in round 5
-  int32_t pad[6];
+  int32_t fc_wtype;      // policy Linear's weights: 0 = 16 bit (version 3), 1 = int8 + per-column f32 scales (version 4)
+  int32_t pad[5];
 };
 static_assert(sizeof(BlobHeader) == 64, "header is 64 bytes");
 
@@ -429,8 +454,10 @@ struct NN {
   float *d_value = nullptr;      // [Gmax]
   ConvW stem, pconv, vconv;
   std::vector<ConvW> c1, c2;
-  uint16_t *fcw = nullptr;
+  uint16_t *fcw = nullptr;       // fc_wtype 1: Np * Kp BYTES of int8 in pair order
   float *fcb = nullptr, *vw = nullptr;
+  float *fcs = nullptr;          // fc_wtype 1: the per-column scales [Np]
+  int fc_wtype = 0;              // the loaded policy Linear's weight type: 0 -> k_fcw / k_fc16, 1 -> k_fcw8
   float *fc_part = nullptr;      // [slabs][Gpad][256 | 384] partial sums of the policy Linear (sized for 2*FC_SPLITK slabs per column)
   int fc_G1 = 0, fc_s1 = FC_SPLITK, fc_s2 = FC_SPLITK;   // work decomposition chosen at load time (plan_fc)
   int fc_layout = 1;                 // the loaded blob's policy-Linear layout: 1 -> k_fc16 (256 x 256 block tiles), 2 -> k_fcw (256 x 384)
@@ -448,7 +475,7 @@ struct NN {
   void *mark_ctx = nullptr;
   float vb = 0.f;
   // dynamic-LDS opt-ins (hipFuncSetAttribute) already made for this engine's device
-  bool attr_conv[2][3] = {{false, false, false}, {false, false, false}}, attr_tower[2] = {false, false}, attr_towerw[2] = {false, false}, attr_fc[2] = {false, false}, attr_gemv = false;
+  bool attr_conv[2][3] = {{false, false, false}, {false, false, false}}, attr_tower[2] = {false, false}, attr_towerw[2] = {false, false}, attr_fc[2] = {false, false}, attr_fc8 = false, attr_gemv = false;
 
   template <class T>
   int dmalloc(T **p, size_t count, std::string *err) {
@@ -534,19 +561,21 @@ struct NN {
     return cus;
   }
   // the shapes this engine runs (the host blob's header and the device pack's descriptor are both held to it); *split: k_fcw's K-split
-  int check_geom(int gF, int gnblocks, int gNp, int gKp, int glayout, int *split, std::string *err) const {
-    return pk_check_geom(gF, gnblocks, gNp, gKp, glayout, dc.A, device_cus(), split, err);
+  int check_geom(int gF, int gnblocks, int gNp, int gKp, int glayout, int gwtype, int *split, std::string *err) const {
+    return pk_check_geom(gF, gnblocks, gNp, gKp, glayout, gwtype, dtype, dc.A, device_cus(), split, err);
   }
-  bool same_geom(int gF, int gnblocks, int gNp, int gKp, int glayout) const {
-    return loaded && F == gF && nblocks == gnblocks && Np == gNp && Kp == gKp && fc_layout == glayout;
+  bool same_geom(int gF, int gnblocks, int gNp, int gKp, int glayout, int gwtype) const {
+    return loaded && F == gF && nblocks == gnblocks && Np == gNp && Kp == gKp && fc_layout == glayout && fc_wtype == gwtype;
   }
   // Frees whatever network was loaded and allocates this one: weights (zeroed), activations, the tower kernels' weight
   // streams; chooses the kernels.  The weights are then written by load() (upload) or by the device pack, and
   // finish_weights() derives the tower streams from them.
-  int alloc_net(int gF, int gnblocks, int gNp, int gKp, int glayout, int split, std::string *err) {
+  int alloc_net(int gF, int gnblocks, int gNp, int gKp, int glayout, int gwtype, int split, std::string *err) {
     destroy();
     F = gF; nblocks = gnblocks; Np = gNp; Kp = gKp;
     fc_layout = glayout;
+    fc_wtype = gwtype;
+    fcs = nullptr;
     fc_gw = fc_layout == 2 ? FCW_COLS : 256;
     if (fc_layout == 2) fc_s1 = split;
     int rc = 0;
@@ -561,7 +590,9 @@ struct NN {
     for (int i = 0; i < nblocks; ++i) { if ((rc = conv(c1[i], F, Fp)) || (rc = conv(c2[i], F, Fp))) return rc; }
     if ((rc = conv(pconv, F, 128))) return rc;
     if ((rc = conv(vconv, F, 128))) return rc;
-    if ((rc = dmalloc(&fcw, (size_t)Np * Kp, err)) || (rc = dmalloc(&fcb, (size_t)Np, err))) return rc;
+    // int8: Np * Kp bytes + Np scales instead of 2 * Np * Kp bytes
+    if ((rc = dmalloc(&fcw, fc_wtype ? (size_t)Np * Kp / 2 : (size_t)Np * Kp, err)) || (rc = dmalloc(&fcb, (size_t)Np, err))) return rc;
+    if (fc_wtype && (rc = dmalloc(&fcs, (size_t)Np, err))) return rc;
     if ((rc = dmalloc(&vw, (size_t)dc.RR * 32, err))) return rc;
     // activations
     const size_t rows = (size_t)Mrows + 2 * guard;
@@ -656,12 +687,13 @@ struct NN {
     if (nbytes < sizeof(BlobHeader)) { *err = "weight blob too small"; return FPC_EWEIGHTS; }
     BlobHeader h;
     memcpy(&h, blob, sizeof(h));
-    if (memcmp(h.magic, "FPCW", 4) || h.version != 3) { *err = "bad weight blob magic/version (this engine reads version 3; version 2 carried the retired 32x32x16 policy-Linear order: export again)"; return FPC_EWEIGHTS; }
+    if (memcmp(h.magic, "FPCW", 4) || (h.version != 3 && h.version != 4)) { *err = "bad weight blob magic/version (this engine reads version 3; version 2 carried the retired 32x32x16 policy-Linear order: export again)"; return FPC_EWEIGHTS; }
     if (h.R != dc.R || h.A_ch != dc.A_ch) { *err = "weight blob is for a different board size"; return FPC_EWEIGHTS; }
     if (h.dtype != dtype) { *err = "weight blob dtype differs from engine nn_dtype"; return FPC_EWEIGHTS; }
     int fcw_split = 0, rc = 0;
-    if ((rc = check_geom(h.F, h.nblocks, h.Np, h.Kp, h.fc_layout, &fcw_split, err))) return rc;
-    if ((rc = alloc_net(h.F, h.nblocks, h.Np, h.Kp, h.fc_layout, fcw_split, err))) return rc;
+    if ((rc = check_geom(h.F, h.nblocks, h.Np, h.Kp, h.fc_layout, h.fc_wtype, &fcw_split, err))) return rc;
+    if (h.fc_wtype != h.version - 3) { *err = "weight blob version and fc_wtype disagree (version 3: 16-bit policy Linear, fc_wtype 0; version 4: int8, fc_wtype 1)"; return FPC_EWEIGHTS; }
+    if ((rc = alloc_net(h.F, h.nblocks, h.Np, h.Kp, h.fc_layout, h.fc_wtype, fcw_split, err))) return rc;
     const unsigned char *base = (const unsigned char *)blob;
     uint64_t off = sizeof(BlobHeader);
     auto take = [&](void *dev, uint64_t bytes) -> int {
@@ -673,7 +705,9 @@ struct NN {
     };
     for (ConvW *cw : convs_in_blob_order())
       if ((rc = take(cw->w, (uint64_t)9 * cw->cout_pad * cw->cin * 2)) || (rc = take(cw->b, (uint64_t)cw->cout_pad * 4))) return rc;
-    if ((rc = take(fcw, (uint64_t)Np * Kp * 2)) || (rc = take(fcb, (uint64_t)Np * 4))) return rc;
+    if ((rc = take(fcw, (uint64_t)Np * Kp * (fc_wtype ? 1 : 2)))) return rc;
+    if (fc_wtype && (rc = take(fcs, (uint64_t)Np * 4))) return rc;
+    if ((rc = take(fcb, (uint64_t)Np * 4))) return rc;
     if ((rc = take(vw, (uint64_t)dc.RR * 32 * 4))) return rc;
     off = (off + 63) & ~63ull;
     if (off + 4 > nbytes) { *err = "weight blob truncated"; return FPC_EWEIGHTS; }
@@ -845,7 +879,16 @@ struct NN {
       }
       // the LIVE instantiations (row tiles and rows at or beyond *n_live return at once) only with a count: fpc_fc.h, FcArgs
       const bool live = in_live_count != nullptr;
-      if (fc_layout == 2 && live) hipLaunchKernelGGL((k_fcw<DT, true>), dim3(blocks, mtiles), dim3(FC_THREADS), FCW_LDS, stream, f);
+      if (fc_wtype) {             // int8 weights: fp16 operands and layout 2 only (check_geom)
+        if (!attr_fc8) {
+          (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_fcw8<false>), hipFuncAttributeMaxDynamicSharedMemorySize, FCW8_LDS);
+          (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_fcw8<true>), hipFuncAttributeMaxDynamicSharedMemorySize, FCW8_LDS);
+          attr_fc8 = true;
+        }
+        Fc8Args f8{f, fcs};
+        if (live) hipLaunchKernelGGL((k_fcw8<true>), dim3(blocks, mtiles), dim3(FC_THREADS), FCW8_LDS, stream, f8);
+        else hipLaunchKernelGGL((k_fcw8<false>), dim3(blocks, mtiles), dim3(FC_THREADS), FCW8_LDS, stream, f8);
+      } else if (fc_layout == 2 && live) hipLaunchKernelGGL((k_fcw<DT, true>), dim3(blocks, mtiles), dim3(FC_THREADS), FCW_LDS, stream, f);
       else if (fc_layout == 2) hipLaunchKernelGGL((k_fcw<DT>), dim3(blocks, mtiles), dim3(FC_THREADS), FCW_LDS, stream, f);
       else if (live) hipLaunchKernelGGL((k_fc16<DT, true>), dim3(blocks, mtiles), dim3(FC_THREADS), FC_LDS, stream, f);
       else hipLaunchKernelGGL((k_fc16<DT>), dim3(blocks, mtiles), dim3(FC_THREADS), FC_LDS, stream, f);
@@ -883,7 +926,8 @@ struct NN {
   // one-time: row-major copy of the policy weights + the legal-logit buffer
   void launch_unfrag() {
     const long chunks = (long)Np * (Kp / 8);
-    if (dtype) hipLaunchKernelGGL((k_fc_unfrag<1>), dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, stream, (const uint16_t *)fcw, fcw2, Np, Kp);   // layouts 1 and 2: one fragment order
+    if (fc_wtype) hipLaunchKernelGGL(k_fc_unfrag8, dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, stream, (const unsigned char *)fcw, fcw2, Np, Kp);
+    else if (dtype) hipLaunchKernelGGL((k_fc_unfrag<1>), dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, stream, (const uint16_t *)fcw, fcw2, Np, Kp);   // layouts 1 and 2: one fragment order
     else hipLaunchKernelGGL((k_fc_unfrag<0>), dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, stream, (const uint16_t *)fcw, fcw2, Np, Kp);
   }
   int ensure_legal_head(std::string *err) {
@@ -905,12 +949,14 @@ struct NN {
     if (!attr) {
       (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_policy_gemv<0>), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
       (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_policy_gemv<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
+      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_policy_gemv<1, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
       attr = true;
     }
     if (lds > 64 * 1024) { *err = "legal-only policy head: activation row does not fit LDS"; return FPC_EINVAL; }
     const int blocks = 768;      // 3 per CU (47 KiB of LDS each at 14x14); pairs are dealt out in equal shares
-    if (dtype) hipLaunchKernelGGL((k_policy_gemv<1>), dim3(blocks), dim3(GEMV_THREADS), lds, stream, dc, t, n, (const uint16_t *)xfc, (const uint16_t *)fcw2, (const float *)fcb, Kp, d_ll);
-    else hipLaunchKernelGGL((k_policy_gemv<0>), dim3(blocks), dim3(GEMV_THREADS), lds, stream, dc, t, n, (const uint16_t *)xfc, (const uint16_t *)fcw2, (const float *)fcb, Kp, d_ll);
+    if (fc_wtype) hipLaunchKernelGGL((k_policy_gemv<1, true>), dim3(blocks), dim3(GEMV_THREADS), lds, stream, dc, t, n, (const uint16_t *)xfc, (const uint16_t *)fcw2, (const float *)fcb, Kp, d_ll, (const float *)fcs);
+    else if (dtype) hipLaunchKernelGGL((k_policy_gemv<1>), dim3(blocks), dim3(GEMV_THREADS), lds, stream, dc, t, n, (const uint16_t *)xfc, (const uint16_t *)fcw2, (const float *)fcb, Kp, d_ll, (const float *)nullptr);
+    else hipLaunchKernelGGL((k_policy_gemv<0>), dim3(blocks), dim3(GEMV_THREADS), lds, stream, dc, t, n, (const uint16_t *)xfc, (const uint16_t *)fcw2, (const float *)fcb, Kp, d_ll, (const float *)nullptr);
     if (hipGetLastError() != hipSuccess) { *err = "k_policy_gemv launch failed"; return FPC_ENODEVICE; }
     return 0;
   }

@@ -171,6 +171,8 @@ _SIGS = {
     "fpc_comm_destroy": (C.c_int, [C.c_void_p]),
     "fpc_comm_available": (C.c_int, []),
     "fpc_nn_kernel": (C.c_char_p, [C.c_void_p]),
+    "fpc_set_fc_weight_type": (C.c_int, [C.c_void_p, C.c_int]),
+    "fpc_nn_fc_kernel": (C.c_char_p, [C.c_void_p]),
     "fpc_allgather_tuples": (C.c_int, [C.c_void_p, P(C.c_int), P(C.c_int)]),
     "fpc_debug_comm_fault": (C.c_int, [C.c_void_p, C.c_int]),
     "fpc_boards_attack_maps": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
@@ -557,12 +559,27 @@ class Engine:
         self._chk(self.L.fpc_weights_blob_size(self.h, int(hidden), int(nblocks), int(fc_layout), C.byref(n)))
         return n.value
 
-    def weights_pack(self, model, fc_layout=None):
-        """the module packed ON THE DEVICE into a version-3 blob, read back: the bytes of
-        weights.export_weights(model, nn_dtype, fc_layout) computed op for op in f32 with correctly rounded divide and
+    def set_fc_weight_type(self, fc_weights):
+        """the policy Linear's weight type of the NEXT weights_blob_size / weights_pack / load_weights_device: "w16" (the
+        default) or "int8" (opt-in: fp16 engines and fc_layout 2 only; include/fpc_engine.h fpc_set_fc_weight_type).
+        Persistent.  load_weights takes the type from the blob's header."""
+        import weights
+        if fc_weights not in weights.FC_WEIGHTS:
+            raise ValueError("fc_weights must be \"w16\" or \"int8\"")
+        self._chk(self.L.fpc_set_fc_weight_type(self.h, weights.FC_WEIGHTS[fc_weights]))
+
+    def nn_fc_kernel(self):
+        """"k_fcw8" | "k_fcw" | "k_fc16": the kernel that runs the policy Linear for the loaded weights ("" before a load)"""
+        return (self.L.fpc_nn_fc_kernel(self.h) or b"").decode()
+
+    def weights_pack(self, model, fc_layout=None, fc_weights=None):
+        """the module packed ON THE DEVICE into a version-3 blob (fc_weights "int8": version 4; None: the type last set),
+        read back: the bytes of weights.export_weights(model, nn_dtype, fc_layout, fc_weights) computed op for op in f32 with correctly rounded divide and
         square root.  Where torch's CPU sqrt is not correctly rounded (0.69 % of random BN variances on the
         build measured) export_weights itself is one unit off in that channel and the two blobs differ there."""
         import torch
+        if fc_weights is not None:
+            self.set_fc_weight_type(fc_weights)
         src, keep, fl = self._net_src(model, fc_layout)
         cap = self.weights_blob_size(src.hidden, src.nblocks, fl)
         buf = torch.empty(cap + 64, dtype=torch.uint8, device="cpu" if self.host_memory else "cuda:%d" % self.device)
@@ -574,9 +591,12 @@ class Engine:
         del keep
         return out
 
-    def load_weights_device(self, model, fc_layout=None):
+    def load_weights_device(self, model, fc_layout=None, fc_weights=None):
         """load_weights(export_weights(model)) without the host: the pack kernels read the module's parameters in device
-        memory and write the engine's weight allocations (in place when the network's geometry has not changed)"""
+        memory and write the engine's weight allocations (in place when the network's geometry has not changed).
+        fc_weights "w16" | "int8": set_fc_weight_type first (None: the type last set, "w16" on a fresh engine)."""
+        if fc_weights is not None:
+            self.set_fc_weight_type(fc_weights)
         src, keep, fl = self._net_src(model, fc_layout)
         self._chk(self.L.fpc_load_weights_device(self.h, C.byref(src), fl))
         del keep

@@ -101,6 +101,14 @@ class MCTS:
         # args["device_weights"] = True (opt-in): a module that lies on the engine's GPU is packed into the engine there
         # (fpc_load_weights_device: no host copy, in place); any other module takes the host path as before
         self.device_weights = bool(args.get("device_weights", False)) if hasattr(args, "get") else False
+        # args["fc_weights"] = "int8" (opt-in; default "w16"): the policy Linear's weights as int8 with one f32 scale per output
+        # (weights.quantize_fc, k_fcw8: half the weight stream and half the engine's largest allocation; it changes the
+        # network's numbers -- tools/fc8_error.py says by how much).  fp16 operands only.
+        self.fc_weights = str(args.get("fc_weights", "w16")) if hasattr(args, "get") else "w16"
+        if self.fc_weights not in ("w16", "int8"):
+            raise ValueError("fc_weights must be \"w16\" or \"int8\", not %r" % (self.fc_weights,))
+        if self.fc_weights == "int8" and self._native and self.nn_dtype != 1:
+            raise ValueError("fc_weights=\"int8\" needs fp16 operands: set args[\"nn_dtype\"] = 1 (bf16 engines have no int8 policy Linear)")
         # args["sim_budget"] (opt-in): None | "per_game" | "visit_target" -- continue_search's per-game budgets (budgets_for)
         self.sim_budget = args.get("sim_budget", None) if hasattr(args, "get") else None
         if self.sim_budget not in SIM_BUDGET_MODES:
@@ -118,9 +126,9 @@ class MCTS:
         ver = _param_version(self.neural_net)
         if getattr(eng, "weights_version", None) != ver:
             if self.device_weights and _on_engine_device(self.neural_net, eng):
-                eng.load_weights_device(self.neural_net)
+                eng.load_weights_device(self.neural_net, fc_weights=self.fc_weights)
             else:
-                eng.load_weights(weights.export_weights(self.neural_net, self.nn_dtype))   # the module stays where it is
+                eng.load_weights(weights.export_weights(self.neural_net, self.nn_dtype, fc_weights=self.fc_weights))   # the module stays where it is
             eng.weights_version = _param_version(self.neural_net)
 
     def add_dirichlet_noise(self, policy, device):

@@ -65,8 +65,33 @@ def default_fc_layout(R):
     return 2 if fcw_split(R) else 1
 
 
-def export_weights(model, dtype=0, fc_layout=None):
-    """model: ResNet in eval semantics.  dtype 0 = bf16, 1 = fp16.  Returns bytes."""
+FC_WEIGHTS = {"w16": 0, "int8": 1}     # the blob header's fc_wtype / include/fpc_engine.h FPC_FC_W16, FPC_FC_W8
+
+
+def quantize_fc(weight_f32, block=1024):
+    """The policy Linear's opt-in 8-bit weights: weight f32 [N, K], one scale per output row n.
+    m_n = max_k |w[n][k]|;  s_n = m_n / 127 (f32, correctly rounded);  m_n < 127 * 2^-100 (zero included): s_n = 1 and the
+    row quantises to zeros;  q[n][k] = clamp(rint(w[n][k] / s_n), -127, 127), ties to even.  -128 is never written.
+    A non-finite weight refuses the export (ValueError).  Returns (q int8 [N, K], scale f32 [N]).  Every op is an f32
+    torch CPU op, so k_pack_fc8 (csrc/fpc_pack.h) reproduces it byte for byte."""
+    w = _cpu(weight_f32)
+    if not bool(torch.isfinite(w).all()):
+        raise ValueError("policy Linear: non-finite weight, int8 export refused")
+    m = w.abs().amax(dim=1)
+    s = m / torch.tensor(127.0, dtype=torch.float32)
+    s = torch.where(m < 127.0 * 2.0 ** -100, torch.ones_like(s), s)
+    q = torch.empty(w.shape, dtype=torch.int8)
+    for r in range(0, w.shape[0], block):      # row blocks: no second f32 copy of a 2.2 GB matrix
+        q[r:r + block] = torch.round(w[r:r + block] / s[r:r + block, None]).clamp_(-127.0, 127.0).to(torch.int8)
+    return q, s
+
+
+def export_weights(model, dtype=0, fc_layout=None, fc_weights="w16"):
+    """model: ResNet in eval semantics.  dtype 0 = bf16, 1 = fp16.  fc_weights "w16" (the default: 16-bit policy-Linear
+    weights, blob version 3) or "int8" (opt-in, fp16 and fc_layout 2 only: quantize_fc, blob version 4).  Returns bytes."""
+    if fc_weights not in FC_WEIGHTS:
+        raise ValueError("fc_weights must be \"w16\" or \"int8\"")
+    wtype = FC_WEIGHTS[fc_weights]
     F = model.startBlock[0].weight.shape[0]
     nblocks = len(model.backBone)
     A_ch = model.policyHead[0].weight.shape[0]
@@ -79,6 +104,8 @@ def export_weights(model, dtype=0, fc_layout=None):
     gw = 384 if fc_layout == 2 else 256
     Np = (A + gw - 1) // gw * gw         # a block owns gw columns
     Kp = (A + 511) // 512 * 512      # k_fc: K/16 k-steps, split-K 4 (8 for the short blocks), 4 k-steps per stage, stages in pairs
+    if wtype and (fc_layout != 2 or dtype != 1):
+        raise ValueError("int8 policy-Linear weights need fp16 operands (dtype 1) and fc_layout 2 (k_fcw8)")
     secs = []
     w, b = _fold(model.startBlock[0], model.startBlock[1])
     Fp = (F + 127) // 128 * 128
@@ -94,18 +121,35 @@ def export_weights(model, dtype=0, fc_layout=None):
     secs += _conv_section(w, b, F, 128, dtype)
     # policy Linear: in index ch*RR+pos -> pos*A_ch+ch ; pad to [Np][Kp]
     fw = _cpu(fc.weight).view(A, A_ch, RR).permute(0, 2, 1).reshape(A, A)
-    t16 = torch.bfloat16 if dtype == 0 else torch.float16
-    fwp = torch.zeros(Np, Kp, dtype=t16)
-    fwp[:A, :A] = fw.to(t16)
-    del fw
     if fc_layout not in (1, 2):
         raise ValueError("fc_layout must be 1 (k_fc16) or 2 (k_fcw); 0 (k_fc) was retired")
-    # MFMA fragment order of k_fc16 / k_fcw (16x16x32): [kstep32][n_tile16][lane = 16*q + c][8],
-    # element (ks, nt, q, c, e) = W'[nt*16 + c][ks*32 + q*8 + e]
-    wf = fwp.view(Np // 16, 16, Kp // 32, 4, 8).permute(2, 0, 3, 1, 4).contiguous()
-    del fwp
-    secs.append(wf.view(torch.int16).numpy().tobytes())
-    del wf
+    if wtype:
+        # int8 in FRAGMENT-PAIR order [kstep32][n_pair32][lane = 16*q + c][2 tiles][8]: element (ks, np, q, c, t, e) =
+        # q8[np*32 + t*16 + c][ks*32 + q*8 + e] -- a lane's 16 bytes are the fragments of two column tiles (k_fcw8);
+        # then the scales f32[Np] (1.0 in the padding)
+        q8, sc = quantize_fc(fw)
+        del fw
+        qp = torch.zeros(Np, Kp, dtype=torch.int8)
+        qp[:A, :A] = q8
+        del q8
+        qf = qp.view(Np // 32, 2, 16, Kp // 32, 4, 8).permute(3, 0, 4, 2, 1, 5).contiguous()
+        del qp
+        secs.append(qf.numpy().tobytes())
+        del qf
+        fs = np.ones(Np, np.float32)
+        fs[:A] = sc.numpy()
+        secs.append(fs.tobytes())
+    else:
+        t16 = torch.bfloat16 if dtype == 0 else torch.float16
+        fwp = torch.zeros(Np, Kp, dtype=t16)
+        fwp[:A, :A] = fw.to(t16)
+        del fw
+        # MFMA fragment order of k_fc16 / k_fcw (16x16x32): [kstep32][n_tile16][lane = 16*q + c][8],
+        # element (ks, nt, q, c, e) = W'[nt*16 + c][ks*32 + q*8 + e]
+        wf = fwp.view(Np // 16, 16, Kp // 32, 4, 8).permute(2, 0, 3, 1, 4).contiguous()
+        del fwp
+        secs.append(wf.view(torch.int16).numpy().tobytes())
+        del wf
     fb = np.zeros(Np, np.float32)
     fb[:A] = _cpu(fc.bias).numpy()
     secs.append(fb.tobytes())
@@ -116,8 +160,10 @@ def export_weights(model, dtype=0, fc_layout=None):
     secs.append(struct.pack("<f", float(_cpu(vfc.bias).item())))
     # version 3: the header word fc_layout names the policy Linear's layout (version 2, rounds 1-2: k_fc's 32x32x16
     # order without that word; an engine of that time refuses version 3, this engine refuses version 2)
-    version = 3
-    out = bytearray(struct.pack("<4s9i24x", b"FPCW", version, R, F, nblocks, dtype, A_ch, Np, Kp, fc_layout))
+    # version 4: the header word fc_wtype (byte 40, the first of version 3's pad words) = 1, the policy-fc section is int8 in
+    # pair order + scales; a blob with fc_wtype 0 IS version 3, byte for byte
+    version = 4 if wtype else 3
+    out = bytearray(struct.pack("<4s10i20x", b"FPCW", version, R, F, nblocks, dtype, A_ch, Np, Kp, fc_layout, wtype))
     assert len(out) == 64
     for s in secs:
         out += b"\0" * ((-len(out)) % 64)

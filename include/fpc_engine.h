@@ -387,6 +387,16 @@ int fpc_weights_pack(fpc_engine *e, const fpc_net_src *src, int fc_layout, void 
  * row-major copy in place and reads the value bias back (4 bytes) -- no hipFree, no hipMalloc.  First load or another
  * geometry: allocates exactly as fpc_load_weights does, then packs.  Emulator build: FPC_EWEIGHTS, as fpc_load_weights. */
 int fpc_load_weights_device(fpc_engine *e, const fpc_net_src *src, int fc_layout);
+/* ---- opt-in int8 weights for the policy Linear (blob version 4, kernel k_fcw8) -- the default stays 16 bit.
+ * Weight type of the policy Linear for the NEXT size / pack / device-load call above (a host blob given to the plain load
+ * call carries its own type in the header).  Persistent.  FPC_EINVAL: null engine, type outside 0..1.
+ * With FPC_FC_W8 those three calls return FPC_EWEIGHTS on a bf16 engine or where fc_layout resolves to 1, and the pack
+ * and the device load return FPC_EWEIGHTS -- nothing written, the loaded network as it was -- if the policy Linear holds
+ * a non-finite weight. */
+enum { FPC_FC_W16 = 0, FPC_FC_W8 = 1 };
+int fpc_set_fc_weight_type(fpc_engine *e, int type);
+/* "k_fcw8" | "k_fcw" | "k_fc16" | "" before a load: the kernel that runs the policy Linear for the loaded weights */
+const char *fpc_nn_fc_kernel(fpc_engine *e);
 /* HIP-event time of the pack kernels of the last fpc_weights_pack / fpc_load_weights_device made with fpc_set_timing on
  * (else FPC_ESTATE) */
 int fpc_weights_pack_ms(fpc_engine *e, float *ms_out);
