@@ -737,6 +737,9 @@ struct NN {
     if (g.cin == 32) return launch_conv_c<DT, 32>(g, M, err);
     if (g.cin == 64) return launch_conv_c<DT, 64>(g, M, err);
     if (g.cin % 128 == 0) return launch_conv_c<DT, 128>(g, M, err);
+    // hidden 192 / 320 / 448: odd multiples of 64 run as 3 / 5 / 7 slabs of 64 channels (the image is restaged per slab,
+    // as the 128-channel slabs of hidden 256 and above are); every width pk_check_geom accepts has a route here
+    if (g.cin % 64 == 0) return launch_conv_c<DT, 64>(g, M, err);
     *err = "unsupported conv input width";
     return FPC_EINVAL;
   }

@@ -294,7 +294,9 @@ inline int pk_check_geom(int F, int nblocks, int Np, int Kp, int layout, int wty
   }
   if (layout < 1 || layout > 2) { *err = "unknown policy-Linear weight layout in weight blob (1 = k_fc16, 2 = k_fcw)"; return FPC_EWEIGHTS; }
   if (F % 64 || F < 64 || F > 512 || nblocks < 0 || Np % (layout == 2 ? PK_FCW_COLS : 256) || Kp % 512 || Kp < 1024 || Np < A || Kp < A) {
-    *err = "unsupported network shape in weight blob (hidden must be a multiple of 64, Np of 256 -- 384 for fc_layout 2 --, Kp of 512)";
+    // every hidden width accepted here forwards (NN::launch_conv: 128 / 256 on the tower kernels, the rest on k_conv3x3 per
+    // layer); a width without a kernel is refused here, at load, never by a later forward
+    *err = "unsupported network shape in weight blob (hidden must be a multiple of 64 in 64..512, Np of 256 -- 384 for fc_layout 2 --, Kp of 512)";
     return FPC_EWEIGHTS;
   }
   *split = 0;

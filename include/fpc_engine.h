@@ -376,7 +376,11 @@ typedef struct fpc_net_src {
  *                 hidden, blocks hidden -> hidden, policy conv hidden -> A_ch, value conv hidden -> 24); cap too small;
  *                 blob_dev not 16-byte aligned; fc_layout outside 0..2;
  *   FPC_EWEIGHTS  a shape fpc_load_weights would refuse (hidden not a multiple of 64 or outside 64..512, layout 2 without
- *                 a one-round split), with its messages. */
+ *                 a one-round split), with its messages.
+ * Every hidden width these calls and fpc_load_weights accept -- 64, 128, ..., 512 -- forwards: 128 and 256 on the tower
+ * kernels, every other one on k_conv3x3 per layer (192 / 320 / 448 as slabs of 64 input channels, 384 / 512 as slabs of
+ * 128).  Held by tests: hidden 64 on every board of 8..14 a side and hidden 192..512 at 8x8 element by element
+ * (tests/test_tower_probe_gpu.py), all eight widths through load + forward (tests/test_nn_gpu.py). */
 /* size of the blob such a network packs into */
 int fpc_weights_blob_size(const fpc_engine *e, int hidden, int nblocks, int fc_layout, uint64_t *nbytes);
 /* header + sections (64-byte aligned, order and padding of csrc/fpc_nn.h's blob comment) into blob_dev[0..cap); exists in

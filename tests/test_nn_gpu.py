@@ -93,7 +93,11 @@ def _positions(R, n):
                                                        (8, 3, 256, 0, 8e-3), (9, 2, 256, 1, 1e-3), (10, 2, 256, 1, 1e-3), (11, 2, 256, 1, 1e-3), (12, 2, 256, 1, 1e-3),
                                                        (13, 2, 256, 1, 1e-3), (14, 2, 256, 1, 1e-3), (14, 2, 256, 0, 8e-3),
                                                        # sizes without a reference layout (hidden 128 off 14x14: k_towerw, MT 3 / 4 / 5 / 6)
-                                                       (9, 2, 128, 1, 1e-3), (11, 2, 128, 1, 1e-3), (12, 2, 128, 1, 1e-3), (13, 2, 128, 1, 1e-3)])
+                                                       (9, 2, 128, 1, 1e-3), (11, 2, 128, 1, 1e-3), (12, 2, 128, 1, 1e-3), (13, 2, 128, 1, 1e-3),
+                                                       # k_conv3x3 per layer off the 8x8 / 14x14 pitches, and at the widths between
+                                                       # and beyond the tower kernels' (3 slabs of 64, 3 and 4 slabs of 128)
+                                                       (10, 2, 64, 1, 1e-3), (13, 2, 64, 0, 8e-3), (8, 2, 192, 1, 1e-3), (9, 2, 384, 1, 1e-3),
+                                                       (8, 2, 512, 1, 1e-3)])
 def test_resnet_forward_vs_torch_fp32(R, blocks, hidden, dtype, tol):
     """north_star tolerance: policy/value logits within 1e-3 of the fp32 reference.  Met with fp16
     MFMA operands; bf16 (8 mantissa bits) is reported with its own, looser, bound."""
@@ -410,7 +414,10 @@ def test_resnet_forward_more_than_256_rows():
                                                   (8, 1, 0, 128), (8, 1, 15, 128), (10, 1, 15, 128), (10, 1, 0, 256), (13, 0, 15, 256),
                                                   # the two shipped hidden-256 instances: configs[3]'s k_towerw<1,256,13,true>
                                                   # (14x14) and the reference default's k_towerw<1,256,4,true> (8x8)
-                                                  (14, 1, 0, 256), (14, 1, 15, 256), (8, 1, 0, 256), (8, 1, 15, 256)])
+                                                  (14, 1, 0, 256), (14, 1, 15, 256), (8, 1, 0, 256), (8, 1, 15, 256),
+                                                  # the per-layer path's k_encode into the bordered grid on odd pitches
+                                                  # (P = 12, 15, 11), the last on three slabs of 64 channels
+                                                  (10, 1, 15, 64), (13, 0, 0, 64), (9, 1, 0, 192)])
 def test_fused_search_equals_stepwise(R, dtype, rules, hidden):
     """fpc_search_run (encode->MFMA net->expand, no host round trip) must give exactly the visit
     counts of the step-wise path fed with the same network's outputs -- under the strict rules and
@@ -650,6 +657,49 @@ def test_native_search_with_dropped_roots_and_weight_reload():
         assert sd[3] < sims and sd[-1] < sims and sd[3] == sd[-1]          # the Q5 roots were dropped early
         assert max(sd) == sims                                              # ... next to games that ran to the end
     assert (res[False]["visits"] == res[True]["visits"]).all() and (res[False]["sims_done"] == res[True]["sims_done"]).all()
+
+
+@pytest.mark.parametrize("hidden", list(range(64, 513, 64)))
+def test_every_accepted_hidden_width_forwards(hidden, monkeypatch):
+    """The contract between load time and forward time: every hidden width the load accepts (the multiples of 64 in
+    64..512, pk_check_geom) forwards -- export, load, one 8-row forward into NaN-filled outputs: no error, every logit
+    and value finite.  Without developer knobs the tuned widths 128 and 256 run k_towerw at 8x8, every other width the
+    per-layer k_conv3x3 (192 / 320 / 448 on slabs of 64 channels, 384 / 512 on slabs of 128)."""
+    import torch
+    import weights
+    monkeypatch.delenv("FPC_DEV_KNOBS", raising=False)
+    R, n = 8, 8
+    m = _model(R, 1, hidden, seed=13)
+    eng = make_engine("gpu", R, INV_OF[R], max_games=n, max_sims=4, nn_dtype=1)
+    try:
+        eng.load_weights(weights.export_weights(m, 1))
+        assert (eng.L.fpc_nn_kernel(eng.h) or b"").decode() == ("k_towerw" if hidden in (128, 256) else "k_conv3x3")
+        x = (torch.rand(n, 24, R, R, generator=torch.Generator().manual_seed(hidden)) < 0.1).float().cuda()
+        lg = torch.full((n, eng.A), float("nan"), device="cuda")
+        va = torch.full((n,), float("nan"), device="cuda")
+        eng.nn_forward(x.data_ptr(), n, lg.data_ptr(), va.data_ptr())      # raises on any error code
+        torch.cuda.synchronize()
+        lg, va = lg.cpu().numpy(), va.cpu().numpy()
+        assert np.isfinite(lg).all() and np.isfinite(va).all(), hidden
+        assert np.abs(lg).max(axis=1).min() > 1e-3                          # every row really was computed
+    finally:
+        eng.close()
+
+
+@pytest.mark.parametrize("hidden", [32, 96, 576])
+def test_hidden_widths_outside_the_contract_are_refused_at_load(hidden):
+    """the other half of the contract: a width that no kernel runs is refused by the LOAD, with a message that names the
+    rule, never by a later forward"""
+    import weights
+    R = 8
+    eng = make_engine("gpu", R, INV_OF[R], max_games=8, max_sims=4, nn_dtype=1)
+    try:
+        with pytest.raises(RuntimeError) as ei:
+            eng.load_weights(weights.export_weights(_model(R, 1, hidden, seed=13), 1))
+        assert "hidden must be a multiple of 64 in 64..512" in str(ei.value), str(ei.value)
+        assert (eng.L.fpc_nn_kernel(eng.h) or b"").decode() == ""           # nothing is loaded
+    finally:
+        eng.close()
 
 
 def test_weight_blob_header_is_checked():

@@ -1,7 +1,8 @@
 """tests/tower_probe.py proven able to fail, without a GPU: the comparators of test_tower_probe_gpu.py are fed the
 reference's own output with one layer mutated the way a tap-loop rewrite goes wrong, and must flag every mutation in
-both weight families; the fp32-order reference must pass; family A's input conditions hold for every GPU case; the
-spliced weight blob is the exported one.  The dense integer Linear of tests/test_linear_probe_gpu.py likewise: its blob
+both weight families; the fp32-order reference must pass; family A's input conditions hold for every GPU case, and its
+value bound flags a misindexed value Linear on every board and width of the per-layer cases; the spliced weight blob is
+the exported one.  The dense integer Linear of tests/test_linear_probe_gpu.py likewise: its blob
 read back with numpy alone, its exactness condition for every GPU case, NO fragment product of its inputs dead, and five
 faults of the Linear's own decomposition flagged."""
 import copy
@@ -14,7 +15,10 @@ import tower_probe as tp
 import weights
 
 # (family, R, hidden, blocks, dtype): the shapes the mutations are tried on (14x14 has the 4-square tail tile)
-SHAPES = [("A", 14, 128, 3, 1), ("A", 14, 128, 2, 0), ("B", 14, 128, 2, 1), ("B", 14, 128, 3, 0), ("B", 8, 128, 2, 1)]
+SHAPES = [("A", 14, 128, 3, 1), ("A", 14, 128, 2, 0), ("B", 14, 128, 2, 1), ("B", 14, 128, 3, 0), ("B", 8, 128, 2, 1),
+          # the per-layer path's own shapes: a width between the tower kernels' (three slabs of 64) on an odd pitch, where
+          # family A draws its 7 nonzeros per output channel from 9 * 192 products, and the same width dense
+          ("A", 9, 192, 3, 1), ("B", 8, 192, 2, 1)]
 
 
 def _case(family, R, hidden, blocks, dtype):
@@ -38,6 +42,22 @@ def test_family_a_conditions_hold_for_every_gpu_case(case):
     values -- asserted inside prepare()"""
     maxima, live, distinct = tp.prepare(case)["conditions"]
     print(tp.case_id(case), "layer maxima", maxima, "nonzero %.2f" % live, "distinct", distinct)
+
+
+@pytest.mark.parametrize("case", [c for c in tp.CASES if c[5] == "A" and c[0] == "k_conv3x3" and not c[6]], ids=tp.case_id)
+def test_family_a_value_bound_sees_a_misindexed_value_linear(case):
+    """The value check of family A (bound: max(value floor, 2 x the CPU fp32 figure), as family B's) proven able to fail
+    on every board and width of the per-layer cases: the value Linear read with rows and columns exchanged (q / R and
+    q % R swapped), and read one square late (an off-by-one pitch), must both leave the bound."""
+    kernel, R, hidden, blocks, dtype, family, knobs, rows = case
+    p = tp.prepare(case)
+    vw, vb = tp.value_vector(R)
+    lim = max(p["value_floor"], 2.0 * p["cpu"]["value"])
+    v = p["ref"]["vconv"]
+    for name, bad in (("transposed", np.swapaxes(v, 2, 3)), ("one square late", np.roll(v.reshape(rows, 24, -1), 1, axis=2))):
+        dv = float(np.abs(tp.value_of(bad, vw, vb) - p["ref_value"]["value"]).max())
+        print("%s, value Linear %s: moves the value by %.3e, bound %.3e" % (tp.case_id(case), name, dv, lim))
+        assert dv > lim, (name, dv, lim)                       # measured: 22 x the bound or more in every case
 
 
 @pytest.mark.parametrize("shape", SHAPES, ids=lambda s: "%s-%dx%d-h%d-b%d-%s" % (s[0], s[1], s[1], s[2], s[3], tp.FMT[s[4]]["name"]))

@@ -34,6 +34,8 @@ def _host_loaded(R, blocks, hidden, dtype, **kw):
 # ---- 1. bytes ------------------------------------------------------------------------------------------------------------
 _BYTES = [(R, hidden, dtype, layout) for R in (8, 9, 11) for hidden in (64, 128) for dtype in (0, 1)
           for layout in ((1, 2) if weights.fcw_split(R) else (1,))]
+# k_pack_conv at the wider shapes: hidden 192 pads the output channels to 256 (cin_pad 192), 256 and 512 pad nothing
+_BYTES += [(8, hidden, 1, weights.default_fc_layout(8)) for hidden in (192, 256, 512)]
 
 
 @pytest.mark.parametrize("R,hidden,dtype,layout", _BYTES)
@@ -62,7 +64,8 @@ def test_pack_follows_the_f32_spec_where_the_host_sqrt_does_not(dtype, monkeypat
 
 
 # ---- 2. forward ----------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("R,hidden,kernel", [(14, 128, "k_towerc"), (8, 128, "k_towerw"), (8, 256, "k_towerw"), (8, 64, "k_conv3x3")])
+@pytest.mark.parametrize("R,hidden,kernel", [(14, 128, "k_towerc"), (8, 128, "k_towerw"), (8, 256, "k_towerw"), (8, 64, "k_conv3x3"),
+                                             (8, 192, "k_conv3x3"), (8, 512, "k_conv3x3")])
 def test_forward_equals_the_host_loaded_engine(R, hidden, kernel):
     """engine X loaded through the host blob, engine Y through fpc_load_weights_device (a FIRST load: it allocates):
     bit-identical logits and values, once per tower path"""

@@ -703,7 +703,8 @@ def linear_case_id(c):
 # ---------------------------------------------------------------------------------------------------------------------
 # the cases of tests/test_tower_probe_gpu.py: (kernel, R, hidden, blocks, dtype, family, developer knobs, rows)
 # Family A depths: 3 blocks with fp16 operands, 2 with bf16 (integers stay below 2^11 / 2^8; test_tower_probe_cpu.py
-# asserts the conditions for every case of this table).  Family B depths: 2, 3, 10 at hidden 128 and 2, 20 at hidden 256.
+# asserts the conditions for every case of this table).  Family B depths: 2, 3, 10 at hidden 128 and 2, 20 at hidden 256;
+# 2 at the per-layer path's widths 64, 192 and 512.
 # ---------------------------------------------------------------------------------------------------------------------
 def _cases():
     out = []
@@ -747,6 +748,24 @@ def _cases():
         for dtype in (1, 0):
             add("k_conv3x3", 14, hidden, 2, dtype, "B", knobs)
     add("k_conv3x3", 8, 64, 3, 1, "A", None, 300)
+    # k_conv3x3 WITHOUT a knob (the product dispatch must choose it), on every board and at every width it serves:
+    # boards 9..13: the bordered grid has 121 / 144 / 169 / 196 / 225 rows per game, so the 256-row blocks straddle games at
+    # another offset in every block, the halo is 12..16 rows and every m / PP, pos / P, pos % P runs on an odd pitch;
+    # 300 rows at 13x13: nearly every block straddles two games
+    for R in (9, 10, 11, 12, 13):
+        both_a("k_conv3x3", R, 64)
+    add("k_conv3x3", 13, 64, 3, 1, "A", None, 300)
+    # widths: 192 / 320 / 448 as 3 / 5 / 7 slabs of 64 channels, 384 / 512 as 3 / 4 slabs of 128 (grid.y 2..4, pitches up to
+    # 1024 bytes); 37 games of PP = 100 are 15 blocks, every block boundary inside a game
+    for hidden in (192, 320, 384, 448, 512):
+        both_a("k_conv3x3", 8, hidden)
+    # an odd pitch and more than one slab at once
+    add("k_conv3x3", 9, 192, 3, 1, "A")
+    add("k_conv3x3", 13, 512, 3, 1, "A")
+    # family A draws 7 of 9 * cin products per output channel; family B touches every one
+    for hidden in (192, 512):
+        for dtype in (1, 0):
+            add("k_conv3x3", 8, hidden, 2, dtype, "B")
     # k_tower on the bordered grid: 14x14 on 8 and on 4 waves, and the sizes k_towerw took over
     for R, knobs in ((14, {"FPC_TOWER_COMPACT": "0"}), (14, {"FPC_TOWER_COMPACT": "0", "FPC_TOWER_WAVES": "4"}),
                      (8, {"FPC_TOWERW": "0"}), (10, {"FPC_TOWERW": "0"}), (13, {"FPC_TOWERW": "0"})):
@@ -786,6 +805,16 @@ def prepare(case):
     p = {"net": m, "x": x, "ref": ref}
     if family == "A":
         p["conditions"] = integer_conditions(ref, dtype)
+        # the value: tanh of the float64 pre-activation, bounded as family B's is.  Every fp32 order of the convolutions
+        # gives the reference's own integers here (rounded and unrounded value conv alike), so the CPU fp32 figure is that
+        # of the value Linear alone
+        vw, vb = value_vector(R)
+        assert np.array_equal(ref["vconv"], ref["vconv_unrounded"])
+        rv = value_of(ref["vconv"], vw, vb)
+        fig = float(np.abs(value_of(ref["vconv"], vw, vb, "f32") - rv).max())
+        p["ref_value"] = {"value": rv, "value_unrounded": rv}
+        p["cpu"] = {"value": fig, "value_unrounded": fig}
+        p["value_floor"] = 2.0 * float(quantum(ref["vconv"].max(), dtype)) * float(np.abs(vw).max())
     else:
         # the CPU figure: the noisiest of a fixed set of fp32 orders.  One order is one draw: on a shallow
         # network the elements more than one rounding away are 0..8 of 10^6 and differ from order to order by more than the
