@@ -77,7 +77,7 @@ struct fpc_engine {
   std::vector<fpc_board> fresh_stage;  // their host staging (the entries at kept positions are not read from the caller)
   // ---- per-game simulation budgets (fpc_search_set_budget)
   int *d_budget = nullptr;        // [max_games], allocated on the first call; t.budget points here while budgets are set
-  std::vector<int> base;          // [G] simulations already through each root: kept_visits - 1 after an advance, else 0
+  std::vector<int> base;          // [G] simulations already through each root: kept_visits - born_visits after an advance, else 0
   bool selected = false;          // a selection has been issued since the last begin / advance
   // ---- live-row numbering (fpc_search_set_live_rows)
   bool live_rows = false;         // the setting; every selection latches it into t.inv (number_live_rows)
@@ -373,6 +373,7 @@ int fpc_create(const fpc_config *cfg, fpc_engine **out) {
   e->cfg = *cfg;
   if (e->cfg.avg_children <= 0) e->cfg.avg_children = 96;
   e->dc = make_devcfg(R, INV, FPC_RULES_STRICT);
+  e->t.born = born_visits(FPC_RULES_STRICT);
   int r = 0;
   auto bail = [&](int code) { g_create_error = e->err; fpc_destroy(e); return code; };
   if (hipStreamCreate(&e->stream) != hipSuccess) { e->err = "hipStreamCreate failed"; return bail(FPC_ENODEVICE); }
@@ -584,12 +585,19 @@ static int admit(fpc_engine *e, int n) {
 
 static LeafPar leafpar(const fpc_engine *e) { return LeafPar{e->d_VL, e->vl}; }
 
+// every selecting kernel exists without and with first-play urgency (fpc_search_set_fpu): the instance the setting asks for
+#define FPC_LAUNCH_SELECT(kernel, e, ...)                         \
+  do {                                                            \
+    if ((e)->t.fpu_mode != FPC_FPU_ZERO) FPC_LAUNCH(kernel<true>, __VA_ARGS__); \
+    else FPC_LAUNCH(kernel<false>, __VA_ARGS__);                  \
+  } while (0)
+
 // k leaves per game (k_select_multi), or one (k_select) in a one-leaf search
 static void launch_select(fpc_engine *e, int k) {
   if (e->multi)
-    FPC_LAUNCH(k_select_multi, e->G, 64, e->stream, e->dc, e->t, e->G, k, e->Cpuct, (const double *)e->d_logtab, leafpar(e));
+    FPC_LAUNCH_SELECT(k_select_multi, e, e->G, 64, e->stream, e->dc, e->t, e->G, k, e->Cpuct, (const double *)e->d_logtab, leafpar(e));
   else
-    FPC_LAUNCH(k_select, e->G, 64, e->stream, e->dc, e->t, e->G, e->Cpuct, (const double *)e->d_logtab);
+    FPC_LAUNCH_SELECT(k_select, e, e->G, 64, e->stream, e->dc, e->t, e->G, e->Cpuct, (const double *)e->d_logtab);
   e->rows_k = k;
   e->pending_vl = e->multi;
 }
@@ -611,20 +619,20 @@ static void launch_expand(fpc_engine *e, const LogitSrc &src, const float *stats
   const double *logtab = e->d_logtab;
   if (e->pending_vl) {
     if (legal && fuse)
-      FPC_LAUNCH(k_expand_legal_select_multi, G, 64, e->stream, e->dc, e->t, G, kexp, ksel, legal, value, e->Cpuct, logtab, leafpar(e));
+      FPC_LAUNCH_SELECT(k_expand_legal_select_multi, e, G, 64, e->stream, e->dc, e->t, G, kexp, ksel, legal, value, e->Cpuct, logtab, leafpar(e));
     else if (legal)
       FPC_LAUNCH(k_expand_legal_multi, G, 64, e->stream, e->dc, e->t, G, kexp, legal, value, leafpar(e));
     else if (fuse)
-      FPC_LAUNCH(k_expand_select_multi, G, EXPAND_THREADS, e->stream, e->dc, e->t, G, kexp, ksel, src, stats, value, e->Cpuct, logtab, leafpar(e));
+      FPC_LAUNCH_SELECT(k_expand_select_multi, e, G, EXPAND_THREADS, e->stream, e->dc, e->t, G, kexp, ksel, src, stats, value, e->Cpuct, logtab, leafpar(e));
     else
       FPC_LAUNCH(k_expand_multi, G, EXPAND_THREADS, e->stream, e->dc, e->t, G, kexp, src, stats, value, leafpar(e));
   } else {
     if (legal && fused)
-      FPC_LAUNCH(k_expand_legal_select, G, 64, e->stream, e->dc, e->t, G, legal, value, e->Cpuct, logtab);
+      FPC_LAUNCH_SELECT(k_expand_legal_select, e, G, 64, e->stream, e->dc, e->t, G, legal, value, e->Cpuct, logtab);
     else if (legal)
       FPC_LAUNCH(k_expand_legal, G, 64, e->stream, e->dc, e->t, G, legal, value);
     else if (fused)
-      FPC_LAUNCH(k_expand_select, G, EXPAND_THREADS, e->stream, e->dc, e->t, G, src, stats, value, e->Cpuct, logtab);
+      FPC_LAUNCH_SELECT(k_expand_select, e, G, EXPAND_THREADS, e->stream, e->dc, e->t, G, src, stats, value, e->Cpuct, logtab);
     else
       FPC_LAUNCH(k_expand, G, EXPAND_THREADS, e->stream, e->dc, e->t, G, src, stats, value);
   }
@@ -771,6 +779,15 @@ int fpc_search_set_leaves(fpc_engine *e, int leaves, double virtual_loss) {
   }
   e->leaves = leaves;
   e->vl = virtual_loss;
+  return 0;
+}
+
+int fpc_search_set_fpu(fpc_engine *e, int mode, double reduction) {
+  if (!e) return fail(e, FPC_EINVAL, "null engine");
+  if (mode != FPC_FPU_ZERO && mode != FPC_FPU_PARENT) return fail(e, FPC_EINVAL, "fpc_search_set_fpu: mode %d outside 0..1", mode);
+  if (!std::isfinite(reduction)) return fail(e, FPC_EINVAL, "fpc_search_set_fpu: reduction must be finite");
+  e->t.fpu_mode = mode;           // read by select_game from the next selection on
+  e->t.fpu_red = reduction;
   return 0;
 }
 
@@ -923,7 +940,8 @@ int fpc_search_grandchildren(fpc_engine *e, int game, int child_idx, int max_chi
 // created with N = 1 and now at N = n has had n - 1 simulations through it, which is the accounting of a fresh root
 // after n - 1 simulations for the log table, the board pool and the node pool, so admit() holds as it is.
 // fpc_search_advance_refill is the same launch with fresh rows among the kept ones (src_game[i] == -1): a fresh
-// root counts as kept with N = 1, i.e. 0 simulations issued.
+// root counts as kept with N = 1, i.e. 0 simulations issued.  Under FPC_RULES_VISITS nodes are born with N = 0 and a root
+// at N = n has had n simulations through it: max(kept) count as issued, a fresh root is kept with N = 0.
 static int advance_impl(fpc_engine *e, const int *src_game, const int *flat, const fpc_board *fresh, int n_games, fpc_board *roots_out,
                         int *kept_visits) {
   USE_DEV(e);
@@ -968,9 +986,10 @@ static int advance_impl(fpc_engine *e, const int *src_game, const int *flat, con
   HIPCHK(e, hipMemcpyAsync(errs.data(), t.err, (size_t)n_games * sizeof(int), hipMemcpyDeviceToHost, e->stream));
   if (roots_out) HIPCHK(e, hipMemcpyAsync(roots_out, e->d_roots, (size_t)n_games * sizeof(fpc_board), hipMemcpyDeviceToHost, e->stream));
   HIPCHK(e, hipStreamSynchronize(e->stream));
-  e->sims_issued = (long)*std::max_element(kept.begin(), kept.end()) - 1;
+  const int born = born_visits(e->dc.rules);      // FPC_RULES_VISITS: a root's N IS the number of simulations through it
+  e->sims_issued = (long)*std::max_element(kept.begin(), kept.end()) - born;
   e->base.resize((size_t)n_games);
-  for (int i = 0; i < n_games; ++i) e->base[i] = std::max(kept[i] - 1, 0);     // per game, for fpc_search_set_budget
+  for (int i = 0; i < n_games; ++i) e->base[i] = std::max(kept[i] - born, 0);     // per game, for fpc_search_set_budget
   if (kept_visits) std::copy(kept.begin(), kept.end(), kept_visits);
   return err_to_status(e, errs, "game");
 }
@@ -1619,10 +1638,16 @@ int fpc_set_policy_mode(fpc_engine *e, int mode) {
   return 0;
 }
 
-int fpc_set_rules(fpc_engine *e, int rules) {
-  if (!e || rules < 0 || rules > FPC_RULES_TRAINING) return fail(e, FPC_EINVAL, "bad rule set");
+// fpc_set_rules keeps the range it always had (0..31); the sets with FPC_RULES_VISITS come in through fpc_set_rule_bits
+static int set_rules_upto(fpc_engine *e, int rules, int top);
+int fpc_set_rules(fpc_engine *e, int rules) { return set_rules_upto(e, rules, FPC_RULES_TRAINING); }
+int fpc_set_rule_bits(fpc_engine *e, int rules) { return set_rules_upto(e, rules, FPC_RULES_SELFPLAY); }
+
+static int set_rules_upto(fpc_engine *e, int rules, int top) {
+  if (!e || rules < 0 || rules > top) return fail(e, FPC_EINVAL, "bad rule set");
   if (e->searching && rules != e->dc.rules) e->searching = false;     // a search in flight was started under the other rules
   e->dc.rules = rules;
+  e->t.born = born_visits(rules);
 #ifndef FPC_EMUL
   e->nn.dc.rules = rules;
 #endif

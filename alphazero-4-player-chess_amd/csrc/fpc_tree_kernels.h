@@ -82,7 +82,17 @@ struct Tree {
   // live-row numbering of the pending selection (fpc_search_set_live_rows, k_live_rows; null: off): [rows] the network row
   // of step row r, -1 for a dead row.  Read by the expansion and k_policy_gemv only.
   const int *inv;
+  // first-play urgency (fpc_search_set_fpu; 0 = FPC_FPU_ZERO: off): the q of a child with N' == 0 in select_game's PUCT branch
+  int fpu_mode;
+  // visit count a node is born with (Q1): 1, or 0 under FPC_RULES_VISITS (the rule setters keep it in step with DevCfg::rules).
+  // Every place that creates a node reads it HERE, as a kernel argument, which costs a scalar load beside the store: derived
+  // from DevCfg::rules up front, the compiler kept it in a register across the whole expansion and spilled that one to
+  // scratch -- a memory round trip in front of the children's stores (0.3 us per step).  The places:
+  // k_search_init, expand_finish, and k_tree_advance's fresh row and its childless root after a failed advance.
+  int born;
+  double fpu_red;
 };
+__host__ __forceinline__ int born_visits(int rules) { return (rules & FPC_RULES_VISITS) ? 0 : 1; }
 
 // ---- LDS image of one wave --------------------------------------------------------------------
 constexpr int GEN_SCR = 14;             // per generator slot: a ray has at most 13 targets; slot 7 of a king: 1 step + 2 castlings
@@ -260,7 +270,8 @@ __device__ __forceinline__ int wave_list_erase_append(uint8_t *list, int len, in
 // mover's castling rights and a rook leaving its home square clears that side's.
 // Wave-cooperative and wave-uniform: every lane derives the same scalars from the LDS board, the piece
 // lists are edited one entry per lane, lane 0 writes the scalars.  All lanes must call.
-// INSTANCE: 0 the one-leaf kernels, 1 the leaf-parallel selection, 2 k_tree_advance, 3 k_play_ply -- separate
+// INSTANCE: 0 the one-leaf kernels, 1 the leaf-parallel selection, 2 k_tree_advance, 3 k_play_ply, 4 / 5 the descents of
+// 0 / 1 with first-play urgency on -- separate
 // instances, so that the one-leaf kernels' callees -- and with them the compiler's inlining decisions and the kernels'
 // ISA -- stay exactly what they were before leaf-parallel search and subtree reuse
 template <int INSTANCE = 0>
@@ -726,7 +737,7 @@ __device__ inline void walk_castle(const fpc_board *b, const DevCfg &c, int from
 //              s->nlegal, and apply the reordering of its full make/undo loop.  Skipped when
 //              do_result found a terminal position (ChooseLeaf returns before the mask is built).
 // `player` < 0 -> side to move.  All lanes of the wave must call this (uniform control flow).
-// INSTANCE: see make_move_wave (0 the one-leaf kernels and k_board_ops, 1 the leaf-parallel selection, 3 k_play_ply)
+// INSTANCE: see make_move_wave (0 the one-leaf kernels and k_board_ops, 1 the leaf-parallel selection, 3 k_play_ply, 4 / 5 first-play urgency)
 template <int INSTANCE = 0>
 __device__ inline void wave_position_ops(WaveLds *s, const DevCfg &c, bool do_result, bool do_legal, int player) {
   const int lane = lane_id();
@@ -1167,7 +1178,7 @@ __global__ void __launch_bounds__(64) k_mask_from_moves(DevCfg c, const fpc_move
 }
 
 // ================================================================================================
-// k_search_init: fresh root per game (mcts.py:29-32: Node(C, game, visit_count=1))
+// k_search_init: fresh root per game (mcts.py:29-32: Node(C, game, visit_count=1); Tree::born)
 // ================================================================================================
 __global__ void __launch_bounds__(64) k_search_init(Tree t, int G, const fpc_board *roots) {
   const int g = blockIdx.x;
@@ -1181,7 +1192,7 @@ __global__ void __launch_bounds__(64) k_search_init(Tree t, int G, const fpc_boa
   }
   if (lane != 0) return;
   const size_t nb = (size_t)g * t.node_cap;
-  t.N[nb] = 1; t.W[nb] = 0.0; t.P[nb] = 0.f; t.mv[nb] = 0xffff; t.parent[nb] = -1; t.child0[nb] = -1; t.nch[nb] = 0;
+  t.N[nb] = t.born; t.W[nb] = 0.0; t.P[nb] = 0.f; t.mv[nb] = 0xffff; t.parent[nb] = -1; t.child0[nb] = -1; t.nch[nb] = 0;
   t.bslot[nb] = 0;
   t.nnodes[g] = 1; t.nboards[g] = 1; t.alive[g] = 1; t.sims_done[g] = 0; t.err[g] = 0;
   t.leaf_node[g] = -1; t.leaf_slot[g] = -1; t.leaf_turn[g] = 0; t.nlegal[g] = 0;
@@ -1248,7 +1259,8 @@ __global__ void __launch_bounds__(256) k_tuples_set_z(fpc_tuple *recs, int count
 //   argmax == 0: weight of child k = powtab[N_k] (pow(N, 1/temperature), tabulated by the host libm); all lanes fetch
 //                the weights into LDS in passes of 64, then ONE lane adds them strictly left to right in f64 -- the
 //                order is the spec (a wave scan rounds differently off temperature 1) -- takes x = uniform * S and
-//                walks the same sums again to the first c_k > x (the last child if there is none);
+//                walks the same sums again to the first c_k > x (the last child if there is none); S == 0 (no child has a
+//                visit: FPC_RULES_VISITS only) picks child min(nc - 1, (int)(uniform * nc));
 //   argmax != 0: the first child with the largest N.
 // A game with a search error or a childless root gets flat = result = -1 and its root state.  A move that cannot be made
 // sets ERR_MOVE in err[] (the call's own array, not t.err) and skips GetGameResult.
@@ -1290,12 +1302,17 @@ __global__ void __launch_bounds__(64) k_play_ply(DevCfg c, Tree t, int G, const 
     } else {
       double S = 0.0;
       for (int k = 0; k < nc; ++k) S = S + wt[k];
-      const double x = u * S;
-      double ck = 0.0;
-      pick = nc - 1;
-      for (int k = 0; k < nc; ++k) {
-        ck = ck + wt[k];
-        if (ck > x) { pick = k; break; }
+      if (S == 0.0) {                                // no child has a visit (FPC_RULES_VISITS only): uniform over the children
+        pick = (int)(u * nc);
+        if (pick > nc - 1) pick = nc - 1;
+      } else {
+        const double x = u * S;
+        double ck = 0.0;
+        pick = nc - 1;
+        for (int k = 0; k < nc; ++k) {
+          ck = ck + wt[k];
+          if (ck > x) { pick = k; break; }
+        }
       }
     }
     s.first_legal = (int)t.mv[nb + c0 + pick];     // broadcast through LDS
@@ -1341,8 +1358,8 @@ __global__ void __launch_bounds__(64) k_replay_store(const fpc_tuple *src, const
 //                    (GetEncodedState per tuple: the sample's own rotation), under the engine's current rule set;
 //   pi[i]  [A]       zero but pi[flat[k]] = (float)visits[k] / (float)S for k < n, S = sum of the visits as an integer;
 //                    one IEEE f32 division, so the row has the bits of tuples.dense_pi (S <= 256 * 65535 < 2^24: torch's
-//                    f32 sum is exact in any order).  n == 0 gives an all-zero row where dense_pi gives NaN -- a finished
-//                    search of a live game never leaves such a record.  A flat >= A (never made by a search) is dropped;
+//                    f32 sum is exact in any order).  n == 0 gives an all-zero row, and so does S == 0 (a root none of whose
+//                    children has a visit, FPC_RULES_VISITS), as in dense_pi.  A flat >= A (never made by a search) is dropped;
 //   z[i]             rec.z.
 // Thread k owns child k (RD_THREADS == FPC_TUPLE_MAXC).  Both rows leave as 16-byte stores, lane after lane (enc and pi
 // rows start on 16-byte boundaries: 24*RR and A = 8(R+1)RR are multiples of 4 floats).  The at most 256 nonzeros of pi
@@ -1396,7 +1413,7 @@ __global__ void __launch_bounds__(RD_THREADS) k_replay_decode(DevCfg c, const fp
   float4 zero;
   zero.x = zero.y = zero.z = zero.w = 0.0f;
   const bool has = tid < nc && flat < c.A;
-  const float val = (float)vis / (float)S;
+  const float val = S > 0 ? (float)vis / (float)S : 0.0f;      // visits that sum to 0 (FPC_RULES_VISITS): a zero row
   for (int q = tid; q < (c.A >> 2); q += RD_THREADS) p4[q] = zero;
   __syncthreads();
   if (has) prow[flat] = val;
@@ -1450,7 +1467,11 @@ struct LeafRow {         // ... and for descent k of a leaf-parallel step
 // MULTI (leaf-parallel, descent k of G games): the per-leaf outputs go to row k*G + g; effective statistics, collision
 // check, leaf_slot holds the GLOBAL pool index g*board_cap + slot, VL += 1 along the path of a live row.
 // M: OneLeaf (m null), or LeafRow (leaf-parallel; m->live is set when the row is live).
-template <class M, bool MULTI = !std::is_same<M, OneLeaf>::value>
+// FPU: first-play urgency is on (fpc_search_set_fpu, FPC_FPU_PARENT).  A separate instance in kernels of its own -- every
+// selecting kernel exists as <false> and <true>, and the host launches the one t.fpu_mode asks for -- so that the kernels
+// without it are instruction for instruction what they were: a lone wave per game pays for every instruction it fetches
+// (both instances in one kernel cost 1 us per step, the extra scalar registers of one shared instance 0.3 us).
+template <class M, bool FPU, bool MULTI = !std::is_same<M, OneLeaf>::value>
 __device__ inline void select_game(WaveLds &s, const DevCfg &c, const Tree &t, int g, double Cpuct, const double *logtab, bool to_next, M *m) {
 #define FPC_ROW (MULTI ? m->k * m->G + g : g)     // the leaf's row (folded to g for one leaf per game)
   const int lane = lane_id();
@@ -1470,6 +1491,12 @@ __device__ inline void select_game(WaveLds &s, const DevCfg &c, const Tree &t, i
   // the count at the start of the step's selection: a descent changes it only at a terminal leaf, which ends the step.
   int room = 1;
   if (t.budget != nullptr) room = t.budget[g] - t.sims_done[g] - (MULTI ? m->k : 0);
+  // First-play urgency (fpc_search_set_fpu): the STORED W and N of the node the descent stands on.  The root's W goes out
+  // with the batch above, and at every deeper level the chosen child's W rides along with best_c0 and the rest -- no
+  // dependent round trip; the instance without it issues neither the load nor the lane read.
+  double Wst = 0.0;
+  if constexpr (FPU) Wst = t.W[nb];
+  int Nst = Nn;
   if constexpr (MULTI) { m->leaf_vl = m->lp.VL[nb]; Nn += m->leaf_vl; }
   if (!is_alive || room <= 0) {             // root already removed from the search (Q5), or the game is at its budget: a dead row
     if (lane == 0) { leaf_node[FPC_ROW] = -1; leaf_slot[FPC_ROW] = -1; }
@@ -1478,6 +1505,8 @@ __device__ inline void select_game(WaveLds &s, const DevCfg &c, const Tree &t, i
   // ---- descent: SelectChild (node.cpp:49-78)
   //   ucb_i = W_i/N_i + C * sqrt( log(sqrt(N_parent)) / (1 + N_i) ) * P_i      (fp64, no contraction)
   //   strict '>' from -inf => lowest index wins ties, NaN never wins
+  //   FPC_RULES_PUCT: -W_i/N_i + C P_i sqrt(N_parent) / (1 + N_i); a child with N_i' == 0 has q = 0, or under
+  //   FPC_FPU_PARENT q = W_p/N_p - reduction from the parent's stored statistics (f64, as written)
   // Every level costs ONE dependent global round trip: the lanes that fetch the children's N/W/P also
   // fetch each child's (first child, child count, board-pool slot, move), so the chosen child's own children can
   // be requested as soon as the argmax is known, and at the leaf its slot, its parent's and its move are at hand.
@@ -1488,9 +1517,12 @@ __device__ inline void select_game(WaveLds &s, const DevCfg &c, const Tree &t, i
     if (lane == 0 && depth < t.path_cap) path[depth] = n;
     ++depth;
     if (c0 < 0) break;
+    // logtab[0] = log(sqrt(0)) is never read: a node with children has been backed up through at least once (its own
+    // expansion), so N >= 1 here under FPC_RULES_VISITS too, where nodes are born with N = 0
     const double L = logtab[Nn];
     const double sqrtNp = sqrt((double)Nn);
-    double best = 0.0;
+    const double q0 = FPU ? Wst / (double)Nst - t.fpu_red : 0.0;     // the q of a child with N' == 0 (PUCT branch)
+    double best = 0.0, best_W = 0.0;
     int besti = -1, best_c0 = -1, best_nc = 0, best_N = 0, best_slot = -1, best_mv = 0xffff;
     if constexpr (MULTI) m->best_vl = 0;
     for (int base = 0; base < nc; base += 64) {
@@ -1498,11 +1530,13 @@ __device__ inline void select_game(WaveLds &s, const DevCfg &c, const Tree &t, i
       double u = 0.0;
       bool valid = false;
       int Nc = 0, cc0 = -1, cnc = 0, cslot = -1, cmv = 0xffff;
+      double Wraw = 0.0;                             // the child's stored W (no virtual loss)
       if constexpr (MULTI) m->cvl = 0;
       if (i < nc) {
         Nc = t.N[nb + c0 + i];
         double Wc = t.W[nb + c0 + i];
         double Pc = (double)t.P[nb + c0 + i];
+        Wraw = Wc;
         if constexpr (MULTI) {                     // N' = N + VL;  W' = W - vl*VL (strict) / W + vl*VL (PUCT: Q = -W/N)
           m->cvl = m->lp.VL[nb + c0 + i];
           Nc += m->cvl;
@@ -1514,7 +1548,7 @@ __device__ inline void select_game(WaveLds &s, const DevCfg &c, const Tree &t, i
         cmv = t.mv[nb + c0 + i];
         if (c.rules & FPC_RULES_PUCT) {
           // AlphaZero PUCT, the child's value seen from the parent: -W/N + C P sqrt(N_parent) / (1 + N)
-          const double q = Nc > 0 ? -(Wc / (double)Nc) : 0.0;
+          const double q = Nc > 0 ? -(Wc / (double)Nc) : q0;
           u = q + Cpuct * Pc * sqrtNp / (double)(1 + Nc);
         } else {
           const double q = Nc > 0 ? Wc / (double)Nc : 0.0;
@@ -1544,6 +1578,10 @@ __device__ inline void select_game(WaveLds &s, const DevCfg &c, const Tree &t, i
         const int w_vl = wave_read(m->cvl, cur);
         if (idx != 0x7fffffff && (besti < 0 || ubest > best)) m->best_vl = w_vl;
       }
+      if constexpr (FPU) {
+        const double w_W = wave_read(Wraw, cur);
+        if (idx != 0x7fffffff && (besti < 0 || ubest > best)) best_W = w_W;
+      }
       if (idx != 0x7fffffff && (besti < 0 || ubest > best)) { best = ubest; besti = idx; best_c0 = w_c0; best_nc = w_nc; best_N = w_N; best_slot = w_slot; best_mv = w_mv; }
     }
     if (besti < 0) { fail = true; break; }
@@ -1551,6 +1589,10 @@ __device__ inline void select_game(WaveLds &s, const DevCfg &c, const Tree &t, i
     c0 = best_c0; nc = best_nc; Nn = best_N;
     parent_slot = slot; slot = best_slot; leaf_mv = best_mv;
     if constexpr (MULTI) m->leaf_vl = m->best_vl;
+    if constexpr (FPU) {
+      Wst = best_W; Nst = best_N;
+      if constexpr (MULTI) Nst -= m->best_vl;                  // best_N is the effective count N + VL
+    }
   }
   FPC_TS(5);
   if (fail) {                                // node.cpp:72-75 throws
@@ -1570,7 +1612,7 @@ __device__ inline void select_game(WaveLds &s, const DevCfg &c, const Tree &t, i
     lds_load_board(&s, &pool[parent_slot]);
     int from;
     const int to = flat_to(c, leaf_mv, &from);
-    const bool moved = make_move_wave<MULTI>(&s.b, from, to, c);
+    const bool moved = make_move_wave<MULTI + (FPU ? 4 : 0)>(&s.b, from, to, c);
     if (lane == 0) {
       int e = moved ? 0 : ERR_MOVE;
       int ns = nboards0;                     // fetched with the root's fields; only this block ever changes it
@@ -1591,7 +1633,7 @@ __device__ inline void select_game(WaveLds &s, const DevCfg &c, const Tree &t, i
   FPC_TS(6);
   // ---- GetGameResult (node.cpp:28-29) then, if in progress, GetLegalMoves
   //      (four_player_chess_board.py:38) on the same state, with their list reorderings
-  wave_position_ops<MULTI>(&s, c, true, true, -1);
+  wave_position_ops<MULTI + (FPU ? 4 : 0)>(&s, c, true, true, -1);
   FPC_TS(12);
   lds_store_board(&s, &t.boards[(size_t)g * t.board_cap + slot]);
   const int res = s.result;
@@ -1634,12 +1676,13 @@ constexpr OneLeaf *ONE_LEAF = nullptr;
 // K descents of one game in one step (leaf-parallel search): row k*G + g for k = 0, 1, ...  The first row that is not
 // live (collision, terminal leaf, dead game, the game's budget reached) ends the game's selection for this step; its
 // remaining rows are dead.
+template <bool FPU>
 __device__ inline void select_game_multi(WaveLds &s, const DevCfg &c, const Tree &t, int G, int g, int K, double Cpuct,
                                          const double *logtab, bool to_next, const LeafPar &lp) {
   int k = 0;
   while (k < K) {
     LeafRow r{lp, k, G, false, 0, 0, 0};
-    select_game(s, c, t, g, Cpuct, logtab, to_next, &r);
+    select_game<LeafRow, FPU>(s, c, t, g, Cpuct, logtab, to_next, &r);
     ++k;
     if (!r.live) break;
     __syncthreads();                         // this descent's tree stores (VL, bslot, nboards, board) precede the next one
@@ -1650,18 +1693,20 @@ __device__ inline void select_game_multi(WaveLds &s, const DevCfg &c, const Tree
     for (; k < K; ++k) { leaf_node[k * G + g] = -1; leaf_slot[k * G + g] = -1; }
 }
 
+template <bool FPU>
 __global__ void __launch_bounds__(64) k_select(DevCfg c, Tree t, int G, double Cpuct, const double *logtab) {
   __shared__ WaveLds s;
   const int g = blockIdx.x;
   if (g >= G) return;
-  select_game(s, c, t, g, Cpuct, logtab, false, ONE_LEAF);
+  select_game<OneLeaf, FPU>(s, c, t, g, Cpuct, logtab, false, ONE_LEAF);
 }
 
+template <bool FPU>
 __global__ void __launch_bounds__(64) k_select_multi(DevCfg c, Tree t, int G, int K, double Cpuct, const double *logtab, LeafPar lp) {
   __shared__ WaveLds s;
   const int g = blockIdx.x;
   if (g >= G) return;
-  select_game_multi(s, c, t, G, g, K, Cpuct, logtab, false, lp);
+  select_game_multi<FPU>(s, c, t, G, g, K, Cpuct, logtab, false, lp);
 }
 
 // pending-visit counters of the roots (node storage, and with it VL, is reused across searches; children are zeroed
@@ -1833,7 +1878,7 @@ __device__ __forceinline__ bool expand_finish(WaveLds &s, const Tree &t, int g, 
     if (nz) {
       const int k = base_node + created + __popcll(bal & ((1ull << lane) - 1ull));
       if (k < t.node_cap) {
-        t.N[nb + k] = 1; t.W[nb + k] = 0.0; t.P[nb + k] = pr; t.mv[nb + k] = s.lsorted[j];
+        t.N[nb + k] = t.born; t.W[nb + k] = 0.0; t.P[nb + k] = pr; t.mv[nb + k] = s.lsorted[j];
         t.parent[nb + k] = n; t.child0[nb + k] = -1; t.nch[nb + k] = 0; t.bslot[nb + k] = -1;
         if constexpr (MULTI) VL[nb + k] = 0;
       }
@@ -1999,6 +2044,7 @@ __global__ void __launch_bounds__(EXPAND_THREADS) k_expand(DevCfg c, Tree t, int
 // dependent-kernel gap less per step).  Other blocks may still be expanding step s when this block's
 // selection publishes its leaf, and strict mode reads the turn of the batch's FIRST live leaf across games
 // (Q6), so the selection writes the _nx leaf arrays; the host swaps them in after the launch.
+template <bool FPU>
 __global__ void __launch_bounds__(EXPAND_THREADS) k_expand_select(DevCfg c, Tree t, int G, LogitSrc logits, const float *stats,
                                                                   const float *value, double Cpuct, const double *logtab) {
   __shared__ WaveLds s;
@@ -2008,7 +2054,7 @@ __global__ void __launch_bounds__(EXPAND_THREADS) k_expand_select(DevCfg c, Tree
   (void)expand_game<false>(s, c, t, G, g, g, logits, stats, value, nullptr);
   __syncthreads();                           // the new children (global stores of other lanes) are visible to the descent
   FPC_TS(4);
-  select_game(s, c, t, g, Cpuct, logtab, true, ONE_LEAF);
+  select_game<OneLeaf, FPU>(s, c, t, g, Cpuct, logtab, true, ONE_LEAF);
 }
 
 
@@ -2053,6 +2099,7 @@ __global__ void __launch_bounds__(64) k_expand_legal(DevCfg c, Tree t, int G, co
 }
 
 // the legal-only head's counterpart of k_expand_select
+template <bool FPU>
 __global__ void __launch_bounds__(64) k_expand_legal_select(DevCfg c, Tree t, int G, const float *ll, const float *value, double Cpuct,
                                                             const double *logtab) {
   __shared__ WaveLds s;
@@ -2060,7 +2107,7 @@ __global__ void __launch_bounds__(64) k_expand_legal_select(DevCfg c, Tree t, in
   if (g >= G) return;
   (void)expand_legal_game<false>(s, c, t, g, g, ll, value, nullptr);
   __syncthreads();
-  select_game(s, c, t, g, Cpuct, logtab, true, ONE_LEAF);
+  select_game<OneLeaf, FPU>(s, c, t, g, Cpuct, logtab, true, ONE_LEAF);
 }
 
 // ================================================================================================
@@ -2090,6 +2137,7 @@ __global__ void __launch_bounds__(EXPAND_THREADS) k_expand_multi(DevCfg c, Tree 
   expand_game_multi<false>(s, c, t, G, g, kexp, logits, nullptr, stats, value, lp.VL);
 }
 
+template <bool FPU>
 __global__ void __launch_bounds__(EXPAND_THREADS) k_expand_select_multi(DevCfg c, Tree t, int G, int kexp, int ksel, LogitSrc logits,
                                                                         const float *stats, const float *value, double Cpuct,
                                                                         const double *logtab, LeafPar lp) {
@@ -2097,7 +2145,7 @@ __global__ void __launch_bounds__(EXPAND_THREADS) k_expand_select_multi(DevCfg c
   const int g = blockIdx.x;
   if (g >= G) return;
   expand_game_multi<false>(s, c, t, G, g, kexp, logits, nullptr, stats, value, lp.VL);
-  select_game_multi(s, c, t, G, g, ksel, Cpuct, logtab, true, lp);
+  select_game_multi<FPU>(s, c, t, G, g, ksel, Cpuct, logtab, true, lp);
 }
 
 __global__ void __launch_bounds__(64) k_expand_legal_multi(DevCfg c, Tree t, int G, int kexp, const float *ll, const float *value, LeafPar lp) {
@@ -2107,13 +2155,14 @@ __global__ void __launch_bounds__(64) k_expand_legal_multi(DevCfg c, Tree t, int
   expand_game_multi<true>(s, c, t, G, g, kexp, LogitSrc{}, ll, nullptr, value, lp.VL);
 }
 
+template <bool FPU>
 __global__ void __launch_bounds__(64) k_expand_legal_select_multi(DevCfg c, Tree t, int G, int kexp, int ksel, const float *ll,
                                                                   const float *value, double Cpuct, const double *logtab, LeafPar lp) {
   __shared__ WaveLds s;
   const int g = blockIdx.x;
   if (g >= G) return;
   expand_game_multi<true>(s, c, t, G, g, kexp, LogitSrc{}, ll, nullptr, value, lp.VL);
-  select_game_multi(s, c, t, G, g, ksel, Cpuct, logtab, true, lp);
+  select_game_multi<FPU>(s, c, t, G, g, ksel, Cpuct, logtab, true, lp);
 }
 
 // ================================================================================================
@@ -2130,8 +2179,8 @@ __global__ void __launch_bounds__(64) k_expand_legal_select_multi(DevCfg c, Tree
 // only region src_game[g] of `t` and writes only region g of `o` and the scalars of game g.
 //
 // FRESH ROWS (fpc_search_advance_refill): src_game[g] == -1 starts a new game in region g on fresh[g], in the state
-// k_search_init leaves a game in (N = 1, W = 0, no children, board slot 0 = fresh[g], one node, one board, alive, no
-// error, no leaf, no pending visit), kept[g] = 1, roots_out[g] = fresh[g]; flat[g] is not read.  A block is one wave
+// k_search_init leaves a game in (N = 1 -- 0 under FPC_RULES_VISITS, as everywhere a node is born --, W = 0, no children, board slot 0 = fresh[g], one node, one board, alive, no
+// error, no leaf, no pending visit), kept[g] = that N, roots_out[g] = fresh[g]; flat[g] is not read.  A block is one wave
 // and src_game[g] is the same in all of its lanes, so the two kinds of row never meet at a barrier: the fresh kind
 // returns before the first __syncthreads, as a block with g >= G does.  Root noise reaches such a root when it is
 // expanded (n == 0), from row g of the noise.
@@ -2143,7 +2192,7 @@ __global__ void __launch_bounds__(64) k_expand_legal_select_multi(DevCfg c, Tree
 // pass get consecutive new board slots (ballot prefix) and their 288-byte states are copied as one flat range of
 // dwords.  No mark array, no atomics, and the node order is a function of the old tree alone.
 // The new root's state is board slot 0: the child's board, or -- a child that was never selected (Q1: every child has
-// N = 1, so a sampled move can be one) -- the old root's board with the move made, which is what a selection would
+// N = 1, so a sampled move can be one; under FPC_RULES_VISITS it has N = 0 and the game is a fresh root's) -- the old root's board with the move made, which is what a selection would
 // have done, and no more (no GetGameResult / legal-moves pass).
 // Root noise: a new root that is already expanded gets it here, child i (ascending flat order) from gamma[g][i], with
 // expand_finish's operations in expand_finish's order; an unexpanded one gets it when it is expanded (n == 0).
@@ -2155,6 +2204,7 @@ __global__ void __launch_bounds__(64) k_tree_advance(DevCfg c, Tree t, Tree o, i
   const int g = blockIdx.x;
   if (g >= G) return;
   const int lane = lane_id();
+  const int born = t.born;
   const int sg = src_game ? src_game[g] : g;
   const size_t nb = (size_t)g * t.node_cap;
   fpc_board *npool = o.boards + (size_t)g * t.board_cap;
@@ -2165,12 +2215,12 @@ __global__ void __launch_bounds__(64) k_tree_advance(DevCfg c, Tree t, Tree o, i
     dst[lane] = w0; out[lane] = w0;
     if (lane < 8) { dst[64 + lane] = w1; out[64 + lane] = w1; }
     if (lane == 0) {
-      o.N[nb] = 1; o.W[nb] = 0.0; o.P[nb] = 0.f; o.mv[nb] = 0xffff; o.parent[nb] = -1; o.child0[nb] = -1; o.nch[nb] = 0;
+      o.N[nb] = born; o.W[nb] = 0.0; o.P[nb] = 0.f; o.mv[nb] = 0xffff; o.parent[nb] = -1; o.child0[nb] = -1; o.nch[nb] = 0;
       o.bslot[nb] = 0;
       if (VL != nullptr) VL[nb] = 0;
       t.nnodes[g] = 1; t.nboards[g] = 1; t.alive[g] = 1; t.sims_done[g] = 0; t.err[g] = 0;
       t.leaf_node[g] = -1; t.leaf_slot[g] = -1; t.leaf_turn[g] = 0; t.nlegal[g] = 0;
-      kept[g] = 1;
+      kept[g] = born;
     }
     return;
   }
@@ -2186,7 +2236,7 @@ __global__ void __launch_bounds__(64) k_tree_advance(DevCfg c, Tree t, Tree o, i
     if (hit) r = rc0 + base + (int)__ffsll((long long)hit) - 1;
   }
   int errbits = r < 0 ? ERR_MOVE : 0;      // not a root child: the game is killed with a childless root on the old root's state
-  const int rslot = r < 0 ? 0 : t.bslot[ob + r], rootN = r < 0 ? 1 : t.N[ob + r];
+  const int rslot = r < 0 ? 0 : t.bslot[ob + r], rootN = r < 0 ? born : t.N[ob + r];
   if (lane == 0) {
     o.N[nb] = rootN; o.W[nb] = r < 0 ? 0.0 : t.W[ob + r]; o.P[nb] = r < 0 ? 0.f : t.P[ob + r]; o.mv[nb] = 0xffff; o.parent[nb] = -1;
     o.child0[nb] = r < 0 ? -1 : t.child0[ob + r]; o.nch[nb] = r < 0 ? (uint16_t)0 : t.nch[ob + r]; o.bslot[nb] = 0;

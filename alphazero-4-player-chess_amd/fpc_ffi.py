@@ -18,6 +18,8 @@ MAX_LEAVES = 8                          # FPC_MAX_LEAVES: leaves per game per st
 REPLAY_RINGS, REPLAY_SCRATCH, REPLAY_COLLECTED, REPLAY_GATHERED = 2, 2, 0, 1     # FPC_REPLAY_*: ring 0 experience, 1 validation
 RULES_STRICT, RULES_PUCT, RULES_ROTATION, RULES_PLANES, RULES_FULL_MOVES, RULES_FIXED = 0, 1, 2, 4, 8, 15
 RULES_TERMINAL, RULES_TRAINING = 16, 31   # Q5 + the terminal value (search past terminal leaves, value by result); FIXED | TERMINAL
+RULES_VISITS, RULES_SELFPLAY = 32, 63     # Q1: N counts backups, every node is born with N = 0; TRAINING | VISITS
+FPU_ZERO, FPU_PARENT = 0, 1               # fpc_search_set_fpu: q of an unvisited child (PUCT): 0, or the parent's Q - reduction
 
 
 class Board(C.Structure):
@@ -157,9 +159,11 @@ _SIGS = {
     "fpc_stream": (C.c_void_p, [C.c_void_p]),
     "fpc_memory_is_host": (C.c_int, []),
     "fpc_set_rules": (C.c_int, [C.c_void_p, C.c_int]),
+    "fpc_set_rule_bits": (C.c_int, [C.c_void_p, C.c_int]),
     "fpc_search_set_root_noise": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_float]),
     "fpc_search_set_leaves": (C.c_int, [C.c_void_p, C.c_int, C.c_double]),
     "fpc_search_set_live_rows": (C.c_int, [C.c_void_p, C.c_int]),
+    "fpc_search_set_fpu": (C.c_int, [C.c_void_p, C.c_int, C.c_double]),
     "fpc_tuples_reserve": (C.c_int, [C.c_void_p, C.c_int]),
     "fpc_tuples_reset": (C.c_int, [C.c_void_p]),
     "fpc_collect_tuples": (C.c_int, [C.c_void_p, P(C.c_int), C.c_int]),
@@ -629,13 +633,25 @@ class Engine:
     # ---- N4: non-strict rule set and root Dirichlet noise (include/fpc_engine.h FPC_RULES_*) ----
     def set_rules(self, rules):
         """0 = strict reference semantics (default); RULES_FIXED = the four corrections of selection, rotation, planes and
-        moves; RULES_TRAINING = those plus RULES_TERMINAL (a terminal leaf is valued by its result and the search goes on)"""
+        moves; RULES_TRAINING = those plus RULES_TERMINAL (a terminal leaf is valued by its result and the search goes on).
+        0..31, as ever; the sets with RULES_VISITS go through set_rule_bits"""
         self._chk(self.L.fpc_set_rules(self.h, int(rules)))
+
+    def set_rule_bits(self, rules):
+        """set_rules over all six bits, 0..63 (include/fpc_engine.h fpc_set_rule_bits): RULES_SELFPLAY = RULES_TRAINING plus
+        RULES_VISITS (every node is born with N = 0: N counts real visits only), or RULES_VISITS with any other bits"""
+        self._chk(self.L.fpc_set_rule_bits(self.h, int(rules)))
 
     def set_leaves(self, k, virtual_loss=1.0):
         """leaf-parallel search (include/fpc_engine.h fpc_search_set_leaves): up to k leaves per game per simulation
         step, kept apart by virtual loss; the step-wise evaluator then sees [k*G, 24, R, R].  k = 1: one leaf per game."""
         self._chk(self.L.fpc_search_set_leaves(self.h, int(k), float(virtual_loss)))
+
+    def set_fpu(self, mode, reduction=0.0):
+        """first-play urgency (include/fpc_engine.h fpc_search_set_fpu): FPU_ZERO (default) or FPU_PARENT -- under RULES_PUCT a
+        child with no visit, pending ones included, gets q = W_p / N_p - reduction of the node above it.  Persistent; without
+        RULES_VISITS no child is ever unvisited and the setting has no effect."""
+        self._chk(self.L.fpc_search_set_fpu(self.h, int(mode), float(reduction)))
 
     def set_live_rows(self, on):
         """live-row numbering (include/fpc_engine.h fpc_search_set_live_rows): every step's live leaves are the network's

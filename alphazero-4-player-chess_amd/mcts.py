@@ -58,9 +58,11 @@ def _on_engine_device(m, eng):
 SIM_BUDGET_MODES = (None, "per_game", "visit_target")
 
 
-def budgets_for(kept, num_searches, max_sims, mode):
+def budgets_for(kept, num_searches, max_sims, mode, born=1):
     """Per-game simulation budgets of one ply (fpc_search_set_budget) from the roots' kept visit counts (1 for a fresh
-    root, so kept - 1 simulations have gone through a root already); None for mode None.
+    root, so kept - 1 simulations have gone through a root already); None for mode None.  born: the visit count a node is
+    born with -- 1, or 0 under fpc_ffi.RULES_VISITS, where `kept` itself is the simulations through the root and stands
+    in place of kept - 1 below.
     "per_game":     min(num_searches, max_sims - (kept - 1)): every game gets num_searches unless ITS OWN kept visits
                     leave less room in the handle -- a fresh row gets its full count beside any kept root.
     "visit_target": max(0, num_searches - (kept - 1)): every root is searched until num_searches simulations have gone
@@ -71,8 +73,8 @@ def budgets_for(kept, num_searches, max_sims, mode):
         return None
     S, M = int(num_searches), int(max_sims)
     if mode == "per_game":
-        return [max(0, min(S, M - (int(k) - 1))) for k in kept]
-    return [max(0, S - (int(k) - 1)) for k in kept]
+        return [max(0, min(S, M - (int(k) - born))) for k in kept]
+    return [max(0, S - (int(k) - born)) for k in kept]
 
 
 class MCTS:
@@ -93,7 +95,13 @@ class MCTS:
         # search), or an int of fpc_ffi.RULES_* bits; args["root_noise"] = True applies Dirichlet(dirichlet_alpha) noise with weight
         # dirichlet_epsilon to the root priors inside the fused search loop, seeded by args["noise_seed"].
         rules = args.get("rules", "strict") if hasattr(args, "get") else "strict"
-        self.rules = {"strict": 0, "fixed": 15, "training": 31}.get(rules, rules)
+        self.rules = {"strict": 0, "fixed": 15, "training": 31, "selfplay": 63}.get(rules, rules)
+        # args["rules"] = "selfplay" (63): "training" plus fpc_ffi.RULES_VISITS -- every node is born with N = 0, so visit
+        # counts, the policy target and Q hold real visits only.  args["fpu"] = None (default) | float: first-play urgency,
+        # an unvisited child's q is the parent's Q minus that reduction (fpc_search_set_fpu; no effect without RULES_VISITS)
+        self.born = 0 if int(self.rules) & 32 else 1
+        fpu = args.get("fpu", None) if hasattr(args, "get") else None
+        self.fpu = None if fpu is None else float(fpu)
         self.root_noise = bool(args.get("root_noise", False)) if hasattr(args, "get") else False
         self._noise_rng = np.random.default_rng(int(args.get("noise_seed", 0))) if self.root_noise else None
         self.leaves = int(args.get("leaves_per_step", 1)) if hasattr(args, "get") else 1
@@ -115,6 +123,12 @@ class MCTS:
             raise ValueError("sim_budget must be one of %r, not %r" % (SIM_BUDGET_MODES, self.sim_budget))
         # args["live_rows"] = True (opt-in): only the live leaves of a step are evaluated (fpc_search_set_live_rows)
         self.live_rows = bool(args.get("live_rows", False)) if hasattr(args, "get") else False
+
+    def _set_fpu(self, eng):
+        if self.fpu is None:
+            eng.set_fpu(0, 0.0)
+        else:
+            eng.set_fpu(1, self.fpu)
 
     def engine_rows(self, G):
         """rows of the engine handle a search of G games needs (G * leaves_per_step)"""
@@ -150,8 +164,9 @@ class MCTS:
         sims = int(self.args["num_searches"])
         eng = az.engine(self.engine_rows(G), sims, self.nn_dtype if self._native else None)
         pods = [g._b for g in games]
-        eng.set_rules(int(self.rules))
+        eng.set_rule_bits(int(self.rules))                 # all six bits; set_rules keeps its range 0..31
         eng.set_leaves(self.leaves, self.virtual_loss)     # the handle is process-wide: set on every search
+        self._set_fpu(eng)
         if self.root_noise:
             import fpc_ffi
             gamma = self._noise_rng.standard_gamma(float(self.args["dirichlet_alpha"]), size=(G, fpc_ffi.MAX_MOVES)).astype(np.float32)
@@ -198,8 +213,9 @@ class MCTS:
         Returns the fpc_ffi.Engine.search_results dict."""
         G = len(flats)
         eng = az.engine()
-        eng.set_rules(int(self.rules))
+        eng.set_rule_bits(int(self.rules))                 # all six bits; set_rules keeps its range 0..31
         eng.set_leaves(self.leaves, self.virtual_loss)
+        self._set_fpu(eng)
         if self.root_noise:
             import fpc_ffi
             gamma = self._noise_rng.standard_gamma(float(self.args["dirichlet_alpha"]), size=(G, fpc_ffi.MAX_MOVES)).astype(np.float32)
@@ -213,13 +229,13 @@ class MCTS:
             kept = eng.search_advance(flats, keep_idx, roots=pods)
         eng.set_live_rows(self.live_rows)
         if budgets is None:
-            budgets = budgets_for(kept, int(self.args["num_searches"]), eng.max_sims, self.sim_budget)
+            budgets = budgets_for(kept, int(self.args["num_searches"]), eng.max_sims, self.sim_budget, self.born)
         if budgets is not None:
             budgets = [int(b) for b in budgets]
             eng.search_set_budget(budgets)
             sims = max(budgets)
         else:
-            sims = min(int(self.args["num_searches"]), eng.max_sims - (int(kept.max()) - 1))
+            sims = min(int(self.args["num_searches"]), eng.max_sims - (int(kept.max()) - self.born))
         if self._native:
             self.sync_weights(eng)
             eng.set_policy_mode(self.policy_head == "legal")

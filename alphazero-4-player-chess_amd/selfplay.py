@@ -41,6 +41,7 @@ def sample_move(flats, visits, temperature, u):
       temperature > 0:  w_k = pow(N_k, 1 / temperature) (libm, f64); c_k = c_{k-1} + w_k strictly left to right;
                         x = u * S with S the last sum; the pick is the first k with c_k > x, else the last child;
       temperature == 0: the first child with the largest N.
+      S == 0 (no child has a visit: fpc_ffi.RULES_VISITS only): child min(n - 1, int(u * n)).
     Differs from sample_action only in rounding (f64 sums of unnormalised weights against f32 probabilities
     renormalised twice): the two pick the same child unless u * S lies within about 1e-5 * S of a c_k."""
     n = len(flats)
@@ -55,6 +56,8 @@ def sample_move(flats, visits, temperature, u):
     total = 0.0
     for x in w:
         total = total + x
+    if total == 0.0:
+        return int(flats[min(n - 1, int(float(u) * n))])
     x = float(u) * total
     c = 0.0
     for k in range(n):

@@ -45,10 +45,12 @@ def unpack_records(R, buf):
 
 
 def dense_pi(rec, A):
-    """alphazero.py:104-110: action_probs[flat] = child visit count; /= sum"""
+    """alphazero.py:104-110: action_probs[flat] = child visit count; /= sum.  Visits that sum to 0 (a root none of whose
+    children has a visit, fpc_ffi.RULES_VISITS) give a zero row, as k_replay_decode does."""
     pi = torch.zeros(A, dtype=torch.float32)
     pi[torch.from_numpy(rec["flat"])] = torch.from_numpy(rec["visits"]).to(torch.float32)
-    return pi / pi.sum()
+    total = pi.sum()
+    return pi / total if total > 0 else pi
 
 
 def all_gather_bytes(payload, device="cpu", group=None):

@@ -127,7 +127,7 @@ int fpc_boards_attack_maps(fpc_engine *e, const fpc_board *boards, int n, uint8_
 int fpc_board_heuristic(const fpc_board *b, int team);
 
 /* ---- MCTS.search (mcts.py:17-43) ---------------------------------------------------------
- * begin:   fresh root per game, visit_count = 1 (mcts.py:29-32); roots uploaded once.
+ * begin:   fresh root per game, visit_count = 1 (mcts.py:29-32; 0 under FPC_RULES_VISITS); roots uploaded once.
  * Then either drive it step by step with an external evaluator (the reference's
  * `neural_net(x) -> (logits, value)` seam, mcts.py:65-66):
  *     for each of num_searches:  fpc_search_select -> evaluator -> fpc_search_expand
@@ -178,9 +178,53 @@ enum {
    *           above.  Budgets and max_sims count terminal backups as before.
    * After a search, alive == 0 then means an error or a terminal root. */
   FPC_RULES_TERMINAL = 16,
-  FPC_RULES_TRAINING = 31    /* FPC_RULES_FIXED | FPC_RULES_TERMINAL */
+  FPC_RULES_TRAINING = 31,   /* FPC_RULES_FIXED | FPC_RULES_TERMINAL */
+  /* Q1 (node.h:28): N counts backups; every node is born with N = 0.  Independent of the five bits above and may be
+   * combined with any of them, strict included.  fpc_abi_version() is unchanged: additions only.
+   *   birth      every node is born with N = 0, W = 0 (clear: N = 1): the children an expansion makes, a fresh root
+   *              (fpc_search_begin), a fresh row of fpc_search_advance_refill and the childless root a failed advance leaves.
+   *   invariant  a node's N is the number of backups through it -- the completed simulations whose path held it,
+   *              expansions plus terminal backups.  After a fresh search in which game g completed s simulations
+   *              root_visits[g] == sims_done[g] == s, and if the root was expanded the children's visits sum to s - 1 (the
+   *              first simulation expanded the root itself).
+   *   selection  the arithmetic is unchanged: both formulas read q = 0 where N' == 0 (but see fpc_search_set_fpu), 1 + N'
+   *              keeps the exploration term finite, and a node with children has N >= 1, so log(sqrt(0)) is never read.
+   *              Under strict rules the first descent below a root with N = 1 sees log(sqrt(1)) = 0 and the lowest index
+   *              wins: specified, not an error.  Virtual loss, collisions, terminal backups (FPC_RULES_TERMINAL: N += 1 on
+   *              every repeat), root noise, both policy heads and live rows are as specified above; none mentions the
+   *              birth count.
+   *   reuse      a never-selected child has N = 0; re-rooted on it the game is in the state of a fresh root.  kept_visits[i]
+   *              is the new root's N as before -- now "simulations through it", 0 for a fresh row and for a never-visited
+   *              child -- and the host's accounting follows: max_i kept_visits[i] simulations count as issued, and
+   *              fpc_search_set_budget's base[g] = kept_visits[g] (clear: both - 1).  Its capacity rule reads
+   *              base[g] + budget[g] > max_sims unchanged.
+   *   play       fpc_search_play's weights are powtab[N_k], powtab[0] = 0 for every temperature > 0.  If S == 0 -- no child
+   *              has a visit; unreachable with the bit clear -- the pick is child min(nc - 1, (int)(uniform * nc)).  At
+   *              temperature 0 the first child with the largest N already gives child 0.
+   *   tuples     fpc_collect_tuples stores all nc pairs, with a visit count of 0 where there were none; a record whose
+   *              visits sum to 0 decodes to a zero pi row (fpc_replay_batch and tuples.dense_pi alike). */
+  FPC_RULES_VISITS = 32,
+  FPC_RULES_SELFPLAY = 63    /* FPC_RULES_TRAINING | FPC_RULES_VISITS */
 };
+/* The five bits above: rules 0..31 (FPC_EINVAL outside, as ever; the call clears FPC_RULES_VISITS). */
 int fpc_set_rules(fpc_engine *e, int rules);
+/* All six bits: rules 0..63 (additions only, fpc_abi_version() unchanged).  fpc_set_rules keeps the range it always had --
+ * a caller that relied on 32 being refused still gets FPC_EINVAL -- and every rule set with FPC_RULES_VISITS goes through
+ * this call; for 0..31 the two calls are the same.  FPC_EINVAL (no state changed): null engine, rules outside 0..63. */
+int fpc_set_rule_bits(fpc_engine *e, int rules);
+/* ---- first-play urgency (opt-in; additions only, fpc_abi_version() unchanged) ---------------------------------------
+ * The value the descent gives a child whose effective count N' = N + VL is 0, in the FPC_RULES_PUCT branch only (the
+ * strict branch keeps q = 0):
+ *   FPC_FPU_ZERO    (default) q = 0: the arithmetic as it always was;
+ *   FPC_FPU_PARENT  q = W_p / (double)N_p - reduction, W_p and N_p the STORED statistics of the node the descent stands on
+ *                   (no virtual loss goes into them; N_p >= 1 because the node has children), f64 without contraction,
+ *                   evaluated as written: the node's value seen by its own side to move, the frame -W_c / N_c already uses
+ *                   for a visited child.  A child with N' > 0 is untouched.
+ * Without FPC_RULES_VISITS every child is born with N = 1, no child ever has N' == 0 and the setting has no effect; it is
+ * accepted all the same.  Persistent, like fpc_search_set_leaves; applies from the next selection.
+ * FPC_EINVAL (no state changed): null engine, mode outside 0..1, reduction not finite. */
+enum { FPC_FPU_ZERO = 0, FPC_FPU_PARENT = 1 };
+int fpc_search_set_fpu(fpc_engine *e, int mode, double reduction);
 /* Root noise for the NEXT searches (mcts.py:45-56 defines add_dirichlet_noise and never calls it):
  * prior'_j = (1 - eps) prior_j + eps g_j / sum_k g_k over the root's legal moves j in ascending flat order,
  * gamma: host array [n_games][FPC_MAX_MOVES] of Gamma(alpha, 1) draws made (and seeded) by the caller;
@@ -480,7 +524,7 @@ int fpc_replay_read(fpc_engine *e, int ring, fpc_tuple *host_out, int first_slot
 /* The batch of the records in slot[0..n-1] (host array; any order, repeats allowed), written to DEVICE memory:
  * enc_dev [n,24,R,R] f32 = GetEncodedState of each record by its own side to move (alphazero.py:71-73) under the engine's
  * current rule set, pi_dev [n,A] f32 = visits / sum(visits) at the record's flat indices and 0 elsewhere (bit-identical to
- * the host path's torch arithmetic; a record with n == 0 gives a zero row), z_dev [n] f32.  Launched on the engine's
+ * the host path's torch arithmetic; a record with n == 0, or whose visits sum to 0, gives a zero row), z_dev [n] f32.  Launched on the engine's
  * stream, which is synchronised before the call returns: any other stream may read the outputs afterwards. */
 int fpc_replay_batch(fpc_engine *e, int ring, const int *slot, int n, float *enc_dev, float *pi_dev, float *z_dev);
 
