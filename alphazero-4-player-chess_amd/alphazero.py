@@ -29,6 +29,9 @@ sim_budget (default None; with reuse_tree) -- per-game simulation budgets for th
 (mcts.budgets_for, fpc_search_set_budget): "per_game" gives every game num_searches unless its own kept visits leave less
 room, so a fresh row is no longer cut short by a kept root beside it; "visit_target" searches every root until
 num_searches simulations have gone through it, kept ones included, and needs a handle of num_searches, not twice that.
+solver (default False; with rules = "training" / "selfplay") -- the MCTS solver (fpc_search_set_solver): the search proves
+wins, losses and draws up the tree, and play() plays a proven win or draw at every temperature -- on the host path from
+fpc_search_proofs (selfplay.proven_pick), on the device_play path inside fpc_search_play.  arena.py does not use it.
 z_from_result (default False: the reference's labels, quirk Q12) -- a game that ends on the board labels its tuples by the
 result (winner's team +1, the other -1, stalemate 0), the value rules = "training" backs up from a terminal leaf.
 """
@@ -122,7 +125,8 @@ class AlphaZero:
         episodes = selfplay.play(search_fn, eng, [g._b for g in games[:G]], self.args, uniforms, continue_fn=continue_fn if reuse else None,
                                  on_searched=on_searched if self.device_replay else None, device_play=device_play,
                                  refill=[g._b for g in games[G:]] if total > G else None,
-                                 z_from_result=bool(self.args.get("z_from_result", False)) if hasattr(self.args, "get") else False)
+                                 z_from_result=bool(self.args.get("z_from_result", False)) if hasattr(self.args, "get") else False,
+                                 solver=self.mcts.solver_in_effect())
         split = self.args["replay_buffer_capacity"] / (self.args["replay_buffer_capacity"] + self.args["validation_buffer_capacity"])
         if self.device_replay:
             z_team = np.zeros((2, len(episodes)), np.float32)      # z by (game, team of the side to move), as the Episodes have it

@@ -83,6 +83,11 @@ struct fpc_engine {
   bool live_rows = false;         // the setting; every selection latches it into t.inv (number_live_rows)
   int *d_live = nullptr;          // [4][max_games] live_row | inv | c_slot | c_turn, then n_live; allocated when first switched on
   int live_n = 0;                 // step entry points: the live rows of the pending selection
+  // ---- MCTS solver (fpc_search_set_solver)
+  bool solver = false;            // the switch; t.S / t2.S (one status byte per node) exist from the first on = 1 and are kept up
+                                  // from then on whatever the switch says: cleared by begin, carried by an advance
+  uint8_t *d_proof = nullptr;     // fpc_search_proofs' staging: [G] roots | [G][max_children] children
+  size_t proof_cap = 0;
   // ---- device-side move choice (fpc_search_play); allocated on the first call
   double *d_powtab = nullptr;     // [max_sims + 16] pow(v, 1 / powtab_T) by the host libm
   double powtab_T = -1.0;         // temperature the uploaded table was made for (-1: none yet)
@@ -546,6 +551,8 @@ int fpc_search_begin(fpc_engine *e, const fpc_board *roots, int n_games, double 
   e->G = n_games;
   e->Cpuct = c_puct;
   HIPCHK(e, hipMemcpyAsync(e->d_roots, roots, (size_t)n_games * sizeof(fpc_board), hipMemcpyHostToDevice, e->stream));
+  if (e->t.S)       // the solver's statuses: every node of the new search is unknown (no kernel gives a node a birth status)
+    HIPCHK(e, hipMemsetAsync(e->t.S, 0, (size_t)n_games * e->t.node_cap, e->stream));
   FPC_LAUNCH(k_search_init, n_games, 64, e->stream, e->t, n_games, (const fpc_board *)e->d_roots);
   HIPCHK(e, hipGetLastError());
   e->searching = true;
@@ -585,11 +592,22 @@ static int admit(fpc_engine *e, int n) {
 
 static LeafPar leafpar(const fpc_engine *e) { return LeafPar{e->d_VL, e->vl}; }
 
-// every selecting kernel exists without and with first-play urgency (fpc_search_set_fpu): the instance the setting asks for
+// the solver is in effect: the switch is on and the rule set holds both FPC_RULES_PUCT and FPC_RULES_TERMINAL
+static bool solving(const fpc_engine *e) {
+  const int need = FPC_RULES_PUCT | FPC_RULES_TERMINAL;
+  return e->solver && e->t.S != nullptr && (e->dc.rules & need) == need;
+}
+
+// every selecting kernel exists without and with first-play urgency (fpc_search_set_fpu) and without and with the solver
+// (fpc_search_set_solver): the instance the settings ask for
 #define FPC_LAUNCH_SELECT(kernel, e, ...)                         \
   do {                                                            \
-    if ((e)->t.fpu_mode != FPC_FPU_ZERO) FPC_LAUNCH(kernel<true>, __VA_ARGS__); \
-    else FPC_LAUNCH(kernel<false>, __VA_ARGS__);                  \
+    const bool fpu_ = (e)->t.fpu_mode != FPC_FPU_ZERO;            \
+    if (solving(e)) {                                             \
+      if (fpu_) FPC_LAUNCH((kernel<true, true>), __VA_ARGS__);      \
+      else FPC_LAUNCH((kernel<false, true>), __VA_ARGS__);          \
+    } else if (fpu_) FPC_LAUNCH((kernel<true, false>), __VA_ARGS__); \
+    else FPC_LAUNCH((kernel<false, false>), __VA_ARGS__);           \
   } while (0)
 
 // k leaves per game (k_select_multi), or one (k_select) in a one-leaf search
@@ -803,6 +821,56 @@ int fpc_search_set_live_rows(fpc_engine *e, int on) {
   return 0;
 }
 
+int fpc_search_set_solver(fpc_engine *e, int on) {
+  if (!e) return fail(e, FPC_EINVAL, "null engine");
+  if (on < 0 || on > 1) return fail(e, FPC_EINVAL, "fpc_search_set_solver: on = %d outside 0..1", on);
+  if (e->searching && e->selected && e->stepping)
+    return fail(e, FPC_ESTATE, "fpc_search_set_solver: a selection has been issued and the search's results have not been read");
+  USE_DEV(e);
+  int r;
+  const size_t nn = (size_t)e->cfg.max_games * e->t.node_cap;
+  if (on && !e->t.S) {              // zeroed by dalloc: a search in progress that has selected nothing holds no proof
+    uint8_t *s1 = nullptr, *s2 = nullptr;
+    if ((r = dalloc(e, &s1, nn))) return r;
+    if (e->t2.N && (r = dalloc(e, &s2, nn))) return r;
+    e->t.S = s1;
+    e->t2.S = s2;
+  }
+  e->solver = on != 0;
+  return 0;
+}
+
+int fpc_search_proofs(fpc_engine *e, int max_children, uint8_t *root_proof, uint8_t *child_proof) {
+  if (!e || !e->searching) return fail(e, FPC_ESTATE, "fpc_search_begin has not been called");
+  if (max_children < 0 || !root_proof) return fail(e, FPC_EINVAL, "fpc_search_proofs: bad max_children or null root_proof");
+  USE_DEV(e);
+  const int G = e->G;
+  const size_t nch = (size_t)G * max_children;
+  if (!e->t.S) {                    // the solver was never switched on
+    std::fill(root_proof, root_proof + G, (uint8_t)FPC_PROOF_UNKNOWN);
+    if (child_proof) std::fill(child_proof, child_proof + nch, (uint8_t)FPC_PROOF_UNKNOWN);
+    return 0;
+  }
+  int r;
+  if ((size_t)G + nch > e->proof_cap) {
+    if (e->d_proof) {
+      (void)hipFree(e->d_proof);
+      e->allocs.erase(std::find(e->allocs.begin(), e->allocs.end(), (void *)e->d_proof));
+      e->d_proof = nullptr;
+    }
+    e->proof_cap = 0;
+    if ((r = dalloc(e, &e->d_proof, (size_t)G + nch))) return r;
+    e->proof_cap = (size_t)G + nch;
+  }
+  uint8_t *d_out = e->d_proof;
+  FPC_LAUNCH(k_root_proofs, G, 64, e->stream, e->t, G, max_children, d_out, d_out + G);
+  HIPCHK(e, hipGetLastError());
+  HIPCHK(e, hipMemcpyAsync(root_proof, d_out, (size_t)G, hipMemcpyDeviceToHost, e->stream));
+  if (child_proof && nch) HIPCHK(e, hipMemcpyAsync(child_proof, d_out + G, nch, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(e, hipStreamSynchronize(e->stream));
+  return 0;
+}
+
 #ifndef FPC_EMUL
 // the pending leaves as the network's input: the tower megakernels encode them themselves, the other paths take k_encode's.
 // Under the live-row numbering the network's row j is the j-th live leaf (k_live_rows' c_slot / c_turn, global pool
@@ -955,6 +1023,7 @@ static int advance_impl(fpc_engine *e, const int *src_game, const int *flat, con
       (!u.mv && (r = dalloc(e, &u.mv, nn))) || (!u.parent && (r = dalloc(e, &u.parent, nn))) || (!u.child0 && (r = dalloc(e, &u.child0, nn))) ||
       (!u.nch && (r = dalloc(e, &u.nch, nn))) || (!u.bslot && (r = dalloc(e, &u.bslot, nn))) ||
       (!u.boards && (r = dalloc(e, &u.boards, (size_t)e->cfg.max_games * t.board_cap))) ||
+      (t.S && !u.S && (r = dalloc(e, &u.S, nn))) ||
       (!e->d_adv && (r = dalloc(e, &e->d_adv, (size_t)2 * e->cfg.max_games))) ||
       (fresh && !e->d_fresh && (r = dalloc(e, &e->d_fresh, (size_t)e->cfg.max_games))))
     return r;
@@ -967,13 +1036,17 @@ static int advance_impl(fpc_engine *e, const int *src_game, const int *flat, con
       if (src_game[i] < 0) e->fresh_stage[i] = fresh[i];
     HIPCHK(e, hipMemcpyAsync(e->d_fresh, e->fresh_stage.data(), (size_t)n_games * sizeof(fpc_board), hipMemcpyHostToDevice, e->stream));
   }
+  if (t.S)          // the statuses travel with the nodes k_tree_advance moves; everything else in the regions written is unknown
+    HIPCHK(e, hipMemsetAsync(u.S, 0, (size_t)n_games * t.node_cap, e->stream));
   Tree o = t;
+  o.S = u.S;
   o.N = u.N; o.W = u.W; o.P = u.P; o.mv = u.mv; o.parent = u.parent; o.child0 = u.child0; o.nch = u.nch; o.bslot = u.bslot; o.boards = u.boards;
   FPC_LAUNCH(k_tree_advance, n_games, 64, e->stream, e->dc, t, o, n_games, src_game ? (const int *)d_src : (const int *)nullptr,
              (const int *)d_flat, fresh ? (const fpc_board *)e->d_fresh : (const fpc_board *)nullptr, e->d_VL, e->d_rc_meta, e->d_roots);
   HIPCHK(e, hipGetLastError());
   std::swap(t.N, u.N); std::swap(t.W, u.W); std::swap(t.P, u.P); std::swap(t.mv, u.mv); std::swap(t.parent, u.parent);
   std::swap(t.child0, u.child0); std::swap(t.nch, u.nch); std::swap(t.bslot, u.bslot); std::swap(t.boards, u.boards);
+  std::swap(t.S, u.S);
   e->G = n_games;
   e->stepping = true;
   e->multi = e->leaves > 1;
@@ -1071,7 +1144,7 @@ int fpc_search_play(fpc_engine *e, double temperature, const double *uniform, in
       if (!ev) HIPCHK(e, hipEventCreate(&ev));
   if (timed) HIPCHK(e, hipEventRecord(e->play_ev[0], e->stream));
   FPC_LAUNCH(k_play_ply, G, 64, e->stream, e->dc, e->t, G, (const double *)e->d_powtab, (int)ntab, argmax ? 1 : 0,
-             (const double *)e->d_play_u, d_flat, d_res, e->d_play_next, d_err);
+             (const double *)e->d_play_u, solving(e) ? 1 : 0, d_flat, d_res, e->d_play_next, d_err);
   HIPCHK(e, hipGetLastError());
   if (timed) HIPCHK(e, hipEventRecord(e->play_ev[1], e->stream));
   std::vector<int> errs(G);

@@ -91,6 +91,11 @@ struct Tree {
   // k_search_init, expand_finish, and k_tree_advance's fresh row and its childless root after a failed advance.
   int born;
   double fpu_red;
+  // proof status per node (fpc_search_set_solver; null until the switch is first turned on): [G][node_cap] FPC_PROOF_*, seen
+  // from the node's own side to move.  Read and written by the SOLVE instances of the selecting kernels only; carried by
+  // k_tree_advance, read by k_play_ply and k_root_proofs.  Nothing gives a node a birth status: the host zeroes the array
+  // (fpc_search_begin, the destination set of an advance), and a status is only ever stored on a node that exists.
+  uint8_t *S;
 };
 __host__ __forceinline__ int born_visits(int rules) { return (rules & FPC_RULES_VISITS) ? 0 : 1; }
 
@@ -271,7 +276,7 @@ __device__ __forceinline__ int wave_list_erase_append(uint8_t *list, int len, in
 // Wave-cooperative and wave-uniform: every lane derives the same scalars from the LDS board, the piece
 // lists are edited one entry per lane, lane 0 writes the scalars.  All lanes must call.
 // INSTANCE: 0 the one-leaf kernels, 1 the leaf-parallel selection, 2 k_tree_advance, 3 k_play_ply, 4 / 5 the descents of
-// 0 / 1 with first-play urgency on -- separate
+// 0 / 1 with first-play urgency on, 8 / 9 / 12 / 13 those four with the solver in effect -- separate
 // instances, so that the one-leaf kernels' callees -- and with them the compiler's inlining decisions and the kernels'
 // ISA -- stay exactly what they were before leaf-parallel search and subtree reuse
 template <int INSTANCE = 0>
@@ -1219,6 +1224,17 @@ __global__ void __launch_bounds__(64) k_root_children(Tree t, int G, int maxc, i
   if (lane == 0) { meta[g * 3 + 0] = t.N[nb]; meta[g * 3 + 1] = nc; meta[g * 3 + 2] = t.sims_done[g]; }
 }
 
+// fpc_search_proofs: the statuses of each root and of its children in the tree's child order
+__global__ void __launch_bounds__(64) k_root_proofs(Tree t, int G, int maxc, uint8_t *root_proof, uint8_t *child_proof) {
+  const int g = blockIdx.x;
+  if (g >= G) return;
+  const int lane = lane_id();
+  const size_t nb = (size_t)g * t.node_cap;
+  const int c0 = t.child0[nb], nc = c0 < 0 ? 0 : (int)t.nch[nb];
+  for (int k = lane; k < maxc; k += 64) child_proof[(size_t)g * maxc + k] = k < nc ? t.S[nb + c0 + k] : (uint8_t)FPC_PROOF_UNKNOWN;
+  if (lane == 0) root_proof[g] = t.S[nb];
+}
+
 // training tuples (alphazero.py:104-112): root mailbox + side to move + sparse pi of a finished search
 __global__ void __launch_bounds__(64) k_collect_tuples(Tree t, int G, const int *game_id, int ply, fpc_tuple *out) {
   const int g = blockIdx.x;
@@ -1265,8 +1281,10 @@ __global__ void __launch_bounds__(256) k_tuples_set_z(fpc_tuple *recs, int count
 // A game with a search error or a childless root gets flat = result = -1 and its root state.  A move that cannot be made
 // sets ERR_MOVE in err[] (the call's own array, not t.err) and skips GetGameResult.
 // ================================================================================================
+// solve != 0 (the solver is in effect): a root proven WIN plays its first child with status LOSS, a root proven DRAW its
+// first child with status DRAW, at every temperature; a root proven LOSS or unknown takes the draw above.
 __global__ void __launch_bounds__(64) k_play_ply(DevCfg c, Tree t, int G, const double *powtab, int powtab_n, int argmax,
-                                                 const double *uniform, int *flat, int *result, fpc_board *next, int *err) {
+                                                 const double *uniform, int solve, int *flat, int *result, fpc_board *next, int *err) {
   __shared__ WaveLds s;
   __shared__ double wt[FPC_MAX_MOVES];
   const int g = blockIdx.x;
@@ -1277,6 +1295,7 @@ __global__ void __launch_bounds__(64) k_play_ply(DevCfg c, Tree t, int G, const 
   int nc = c0 < 0 ? 0 : (int)t.nch[nb];
   if (nc > FPC_MAX_MOVES) nc = FPC_MAX_MOVES;
   const double u = uniform[g];
+  const int rootS = solve ? (int)t.S[nb] : FPC_PROOF_UNKNOWN;
   lds_load_board(&s, &t.boards[(size_t)g * t.board_cap]);
   if (gerr != 0 || nc == 0) {
     lds_store_board(&s, &next[g]);
@@ -1292,10 +1311,22 @@ __global__ void __launch_bounds__(64) k_play_ply(DevCfg c, Tree t, int G, const 
       wt[k] = argmax ? (double)n : powtab[n < 0 ? 0 : n < powtab_n ? n : powtab_n - 1];
     }
   }
+  // the solver's pick: the first child with the status a proven root asks for (-1: none, the draw decides)
+  int forced = -1;
+  if (rootS == FPC_PROOF_WIN || rootS == FPC_PROOF_DRAW) {       // wave-uniform
+    const int want = rootS == FPC_PROOF_WIN ? FPC_PROOF_LOSS : FPC_PROOF_DRAW;
+    for (int base = 0; base < nc && forced < 0; base += 64) {
+      const int k = base + lane;
+      const unsigned long long hit = __ballot(k < nc && (int)t.S[nb + c0 + k] == want);
+      if (hit) forced = base + (int)__ffsll((long long)hit) - 1;
+    }
+  }
   __syncthreads();
   if (lane == 0) {
     int pick = 0;
-    if (argmax) {
+    if (forced >= 0) {
+      pick = forced;
+    } else if (argmax) {
       double best = wt[0];
       for (int k = 1; k < nc; ++k)
         if (wt[k] > best) { best = wt[k]; pick = k; }
@@ -1447,6 +1478,41 @@ __device__ __forceinline__ void backprop_path(const Tree &t, size_t nb, int g, f
   }
 }
 
+// The MCTS solver (fpc_search_set_solver).  pv: the value a proven node backs up, from its own side to move.
+__device__ __forceinline__ float proof_value(int st) { return st == FPC_PROOF_WIN ? 1.0f : st == FPC_PROOF_LOSS ? -1.0f : 0.0f; }
+
+// Node `cn` has just been proven `cs` (all 64 lanes call with the same arguments): store it and carry the proof towards
+// the root.  With c the node just proven and p its parent: stop without a parent or at a p that is proven already; c LOSS
+// makes p WIN; otherwise p's children are read 64 per pass (at most FPC_MAX_MOVES / 64 passes) and combined with ballots --
+// one unknown child stops the walk, all WIN make p LOSS, anything else DRAW.  The status just given to c is taken from
+// the register, not read back: lane 0's store need not be visible to the other lanes.  A status never changes once set.
+__device__ __forceinline__ void prove_upward(const Tree &t, size_t nb, int cn, int cs) {
+  const int lane = lane_id();
+  for (;;) {
+    if (lane == 0) t.S[nb + cn] = (uint8_t)cs;
+    const int p = t.parent[nb + cn];
+    if (p < 0) return;
+    // p's status as LANE 0 sees it, for every lane: lane 0 is the only writer, and nothing orders its stores against
+    // the other lanes' loads -- a lane that read S[p] after lane 0 had gone on to prove p would leave the walk alone
+    const int pS = wave_read((int)t.S[nb + p], 0), pc0 = t.child0[nb + p], pnc = t.nch[nb + p];
+    if (pS != FPC_PROOF_UNKNOWN) return;
+    int ps = FPC_PROOF_WIN;
+    if (cs != FPC_PROOF_LOSS) {
+      bool all_win = true;
+      for (int base = 0; base < pnc; base += 64) {
+        const int i = base + lane;
+        int st = FPC_PROOF_WIN;                // lanes past the children: neutral
+        if (i < pnc) st = pc0 + i == cn ? cs : (int)t.S[nb + pc0 + i];
+        if (__ballot(st == FPC_PROOF_UNKNOWN)) return;
+        if (__ballot(st != FPC_PROOF_WIN)) all_win = false;
+      }
+      ps = all_win ? FPC_PROOF_LOSS : FPC_PROOF_DRAW;
+    }
+    cn = p;
+    cs = ps;
+  }
+}
+
 // Leaf-parallel search (fpc_search_set_leaves, K leaves per game per step): row r = k*G + g holds the k-th leaf game g
 // selected in this step.  VL [G][node_cap] counts the pending visits of a node (0 outside a step); the descent sees
 // N' = N + VL and W' = W -+ vl*VL (lower Q on pending paths), a descent that ends on a pending leaf is a collision.
@@ -1471,7 +1537,16 @@ struct LeafRow {         // ... and for descent k of a leaf-parallel step
 // selecting kernel exists as <false> and <true>, and the host launches the one t.fpu_mode asks for -- so that the kernels
 // without it are instruction for instruction what they were: a lone wave per game pays for every instruction it fetches
 // (both instances in one kernel cost 1 us per step, the extra scalar registers of one shared instance 0.3 us).
-template <class M, bool FPU, bool MULTI = !std::is_same<M, OneLeaf>::value>
+// SOLVE: the MCTS solver is in effect (fpc_search_set_solver under FPC_RULES_PUCT | FPC_RULES_TERMINAL), for
+// the same reason a second switch of the same kind: every selecting kernel exists as <FPU, SOLVE> in four instances, and the
+// <*, false> ones neither load nor store a status.  t.S is not null in a SOLVE instance (the host launches one only then).
+//   1. a root with children and a status: a dead row, nothing is written (the status rides with the root's other fields);
+//   2. a child with status WIN is no candidate of the argmax (its status rides with its N / W / P / child0);
+//   3. a chosen child with a status ends the descent: pv(status) is backed up from it, sims_done += 1, a dead row that
+//      ends the game's selection of the step -- before the collision check;
+//   4. an unknown leaf whose game is over: the terminal backup, then the leaf's status from the value backed up and the
+//      proof's way up (prove_upward).
+template <class M, bool FPU, bool SOLVE, bool MULTI = !std::is_same<M, OneLeaf>::value>
 __device__ inline void select_game(WaveLds &s, const DevCfg &c, const Tree &t, int g, double Cpuct, const double *logtab, bool to_next, M *m) {
 #define FPC_ROW (MULTI ? m->k * m->G + g : g)     // the leaf's row (folded to g for one leaf per game)
   const int lane = lane_id();
@@ -1497,10 +1572,18 @@ __device__ inline void select_game(WaveLds &s, const DevCfg &c, const Tree &t, i
   double Wst = 0.0;
   if constexpr (FPU) Wst = t.W[nb];
   int Nst = Nn;
+  int rootS = 0;                             // the solver: the root's status, with the batch above
+  if constexpr (SOLVE) rootS = t.S[nb];
   if constexpr (MULTI) { m->leaf_vl = m->lp.VL[nb]; Nn += m->leaf_vl; }
   if (!is_alive || room <= 0) {             // root already removed from the search (Q5), or the game is at its budget: a dead row
     if (lane == 0) { leaf_node[FPC_ROW] = -1; leaf_slot[FPC_ROW] = -1; }
     return;
+  }
+  if constexpr (SOLVE) {
+    if (c0 >= 0 && rootS != FPC_PROOF_UNKNOWN) {     // a proven root with children: idle like a game at its budget
+      if (lane == 0) { leaf_node[FPC_ROW] = -1; leaf_slot[FPC_ROW] = -1; }
+      return;
+    }
   }
   // ---- descent: SelectChild (node.cpp:49-78)
   //   ucb_i = W_i/N_i + C * sqrt( log(sqrt(N_parent)) / (1 + N_i) ) * P_i      (fp64, no contraction)
@@ -1512,6 +1595,7 @@ __device__ inline void select_game(WaveLds &s, const DevCfg &c, const Tree &t, i
   // be requested as soon as the argmax is known, and at the leaf its slot, its parent's and its move are at hand.
   int n = 0, depth = 0, leaf_mv = 0xffff;
   bool fail = false;
+  int proven = FPC_PROOF_UNKNOWN;            // the solver: the status of the proven child the descent ended on
   int *path = t.path + (size_t)FPC_ROW * t.path_cap;
   for (;;) {
     if (lane == 0 && depth < t.path_cap) path[depth] = n;
@@ -1524,6 +1608,7 @@ __device__ inline void select_game(WaveLds &s, const DevCfg &c, const Tree &t, i
     const double q0 = FPU ? Wst / (double)Nst - t.fpu_red : 0.0;     // the q of a child with N' == 0 (PUCT branch)
     double best = 0.0, best_W = 0.0;
     int besti = -1, best_c0 = -1, best_nc = 0, best_N = 0, best_slot = -1, best_mv = 0xffff;
+    int best_S = FPC_PROOF_UNKNOWN;
     if constexpr (MULTI) m->best_vl = 0;
     for (int base = 0; base < nc; base += 64) {
       const int i = base + lane;
@@ -1531,8 +1616,10 @@ __device__ inline void select_game(WaveLds &s, const DevCfg &c, const Tree &t, i
       bool valid = false;
       int Nc = 0, cc0 = -1, cnc = 0, cslot = -1, cmv = 0xffff;
       double Wraw = 0.0;                             // the child's stored W (no virtual loss)
+      int cS = FPC_PROOF_UNKNOWN;                    // the child's status
       if constexpr (MULTI) m->cvl = 0;
       if (i < nc) {
+        if constexpr (SOLVE) cS = t.S[nb + c0 + i];
         Nc = t.N[nb + c0 + i];
         double Wc = t.W[nb + c0 + i];
         double Pc = (double)t.P[nb + c0 + i];
@@ -1556,6 +1643,7 @@ __device__ inline void select_game(WaveLds &s, const DevCfg &c, const Tree &t, i
           u = q + e * Pc;
         }
         valid = u > -__builtin_inf();
+        if constexpr (SOLVE) valid = valid & (cS != FPC_PROOF_WIN);      // the move that loses is no candidate
       }
       // argmax with the reference's rule (strict '>': the FIRST maximum wins): start at the lowest valid lane and jump
       // to the lowest lane that beats the current one until none does -- about ln(children) rounds of two scalar lane
@@ -1582,6 +1670,10 @@ __device__ inline void select_game(WaveLds &s, const DevCfg &c, const Tree &t, i
         const double w_W = wave_read(Wraw, cur);
         if (idx != 0x7fffffff && (besti < 0 || ubest > best)) best_W = w_W;
       }
+      if constexpr (SOLVE) {
+        const int w_S = wave_read(cS, cur);
+        if (idx != 0x7fffffff && (besti < 0 || ubest > best)) best_S = w_S;
+      }
       if (idx != 0x7fffffff && (besti < 0 || ubest > best)) { best = ubest; besti = idx; best_c0 = w_c0; best_nc = w_nc; best_N = w_N; best_slot = w_slot; best_mv = w_mv; }
     }
     if (besti < 0) { fail = true; break; }
@@ -1593,11 +1685,25 @@ __device__ inline void select_game(WaveLds &s, const DevCfg &c, const Tree &t, i
       Wst = best_W; Nst = best_N;
       if constexpr (MULTI) Nst -= m->best_vl;                  // best_N is the effective count N + VL
     }
+    if constexpr (SOLVE) {
+      if (best_S != FPC_PROOF_UNKNOWN) { proven = best_S; break; }   // the descent ends on a proven child
+    }
   }
   FPC_TS(5);
   if (fail) {                                // node.cpp:72-75 throws
     if (lane == 0) { t.err[g] |= ERR_SELECT; t.alive[g] = 0; leaf_node[FPC_ROW] = -1; leaf_slot[FPC_ROW] = -1; }
     return;
+  }
+  if constexpr (SOLVE) {
+    if (proven != FPC_PROOF_UNKNOWN) {       // the bookkeeping of a terminal backup: no board, no GetGameResult, no move generation
+      if (lane == 0) {
+        backprop_lane0(t, nb, n, proof_value(proven));
+        t.sims_done[g] += 1;
+        leaf_node[FPC_ROW] = -1;
+        leaf_slot[FPC_ROW] = -1;
+      }
+      return;
+    }
   }
   if constexpr (MULTI) {
     if (m->leaf_vl > 0) {                    // collision: a leaf already taken in this step; nothing is touched
@@ -1612,7 +1718,7 @@ __device__ inline void select_game(WaveLds &s, const DevCfg &c, const Tree &t, i
     lds_load_board(&s, &pool[parent_slot]);
     int from;
     const int to = flat_to(c, leaf_mv, &from);
-    const bool moved = make_move_wave<MULTI + (FPU ? 4 : 0)>(&s.b, from, to, c);
+    const bool moved = make_move_wave<MULTI + (FPU ? 4 : 0) + (SOLVE ? 8 : 0)>(&s.b, from, to, c);
     if (lane == 0) {
       int e = moved ? 0 : ERR_MOVE;
       int ns = nboards0;                     // fetched with the root's fields; only this block ever changes it
@@ -1633,7 +1739,7 @@ __device__ inline void select_game(WaveLds &s, const DevCfg &c, const Tree &t, i
   FPC_TS(6);
   // ---- GetGameResult (node.cpp:28-29) then, if in progress, GetLegalMoves
   //      (four_player_chess_board.py:38) on the same state, with their list reorderings
-  wave_position_ops<MULTI + (FPU ? 4 : 0)>(&s, c, true, true, -1);
+  wave_position_ops<MULTI + (FPU ? 4 : 0) + (SOLVE ? 8 : 0)>(&s, c, true, true, -1);
   FPC_TS(12);
   lds_store_board(&s, &t.boards[(size_t)g * t.board_cap + slot]);
   const int res = s.result;
@@ -1651,6 +1757,11 @@ __device__ inline void select_game(WaveLds &s, const DevCfg &c, const Tree &t, i
       if (leaves) t.alive[g] = 0;
       leaf_node[FPC_ROW] = -1;
       leaf_slot[FPC_ROW] = -1;
+    }
+    if constexpr (SOLVE) {                   // the leaf's status from the value just backed up (FPC_RULES_TERMINAL's: the solver
+                                             // is in effect only under it), recomputed by every lane: the branch is wave-uniform
+      const int st = res == FPC_STALEMATE ? FPC_PROOF_DRAW : (res == FPC_WIN_BG ? 1 : 0) == (s.b.turn & 1) ? FPC_PROOF_WIN : FPC_PROOF_LOSS;
+      prove_upward(t, nb, n, st);
     }
     return;
   }
@@ -1675,14 +1786,14 @@ constexpr OneLeaf *ONE_LEAF = nullptr;
 
 // K descents of one game in one step (leaf-parallel search): row k*G + g for k = 0, 1, ...  The first row that is not
 // live (collision, terminal leaf, dead game, the game's budget reached) ends the game's selection for this step; its
-// remaining rows are dead.
-template <bool FPU>
+// remaining rows are dead.  With the solver a proven root and a backup from a proven child end it the same way.
+template <bool FPU, bool SOLVE>
 __device__ inline void select_game_multi(WaveLds &s, const DevCfg &c, const Tree &t, int G, int g, int K, double Cpuct,
                                          const double *logtab, bool to_next, const LeafPar &lp) {
   int k = 0;
   while (k < K) {
     LeafRow r{lp, k, G, false, 0, 0, 0};
-    select_game<LeafRow, FPU>(s, c, t, g, Cpuct, logtab, to_next, &r);
+    select_game<LeafRow, FPU, SOLVE>(s, c, t, g, Cpuct, logtab, to_next, &r);
     ++k;
     if (!r.live) break;
     __syncthreads();                         // this descent's tree stores (VL, bslot, nboards, board) precede the next one
@@ -1693,20 +1804,20 @@ __device__ inline void select_game_multi(WaveLds &s, const DevCfg &c, const Tree
     for (; k < K; ++k) { leaf_node[k * G + g] = -1; leaf_slot[k * G + g] = -1; }
 }
 
-template <bool FPU>
+template <bool FPU, bool SOLVE>
 __global__ void __launch_bounds__(64) k_select(DevCfg c, Tree t, int G, double Cpuct, const double *logtab) {
   __shared__ WaveLds s;
   const int g = blockIdx.x;
   if (g >= G) return;
-  select_game<OneLeaf, FPU>(s, c, t, g, Cpuct, logtab, false, ONE_LEAF);
+  select_game<OneLeaf, FPU, SOLVE>(s, c, t, g, Cpuct, logtab, false, ONE_LEAF);
 }
 
-template <bool FPU>
+template <bool FPU, bool SOLVE>
 __global__ void __launch_bounds__(64) k_select_multi(DevCfg c, Tree t, int G, int K, double Cpuct, const double *logtab, LeafPar lp) {
   __shared__ WaveLds s;
   const int g = blockIdx.x;
   if (g >= G) return;
-  select_game_multi<FPU>(s, c, t, G, g, K, Cpuct, logtab, false, lp);
+  select_game_multi<FPU, SOLVE>(s, c, t, G, g, K, Cpuct, logtab, false, lp);
 }
 
 // pending-visit counters of the roots (node storage, and with it VL, is reused across searches; children are zeroed
@@ -2044,7 +2155,7 @@ __global__ void __launch_bounds__(EXPAND_THREADS) k_expand(DevCfg c, Tree t, int
 // dependent-kernel gap less per step).  Other blocks may still be expanding step s when this block's
 // selection publishes its leaf, and strict mode reads the turn of the batch's FIRST live leaf across games
 // (Q6), so the selection writes the _nx leaf arrays; the host swaps them in after the launch.
-template <bool FPU>
+template <bool FPU, bool SOLVE>
 __global__ void __launch_bounds__(EXPAND_THREADS) k_expand_select(DevCfg c, Tree t, int G, LogitSrc logits, const float *stats,
                                                                   const float *value, double Cpuct, const double *logtab) {
   __shared__ WaveLds s;
@@ -2054,7 +2165,7 @@ __global__ void __launch_bounds__(EXPAND_THREADS) k_expand_select(DevCfg c, Tree
   (void)expand_game<false>(s, c, t, G, g, g, logits, stats, value, nullptr);
   __syncthreads();                           // the new children (global stores of other lanes) are visible to the descent
   FPC_TS(4);
-  select_game<OneLeaf, FPU>(s, c, t, g, Cpuct, logtab, true, ONE_LEAF);
+  select_game<OneLeaf, FPU, SOLVE>(s, c, t, g, Cpuct, logtab, true, ONE_LEAF);
 }
 
 
@@ -2099,7 +2210,7 @@ __global__ void __launch_bounds__(64) k_expand_legal(DevCfg c, Tree t, int G, co
 }
 
 // the legal-only head's counterpart of k_expand_select
-template <bool FPU>
+template <bool FPU, bool SOLVE>
 __global__ void __launch_bounds__(64) k_expand_legal_select(DevCfg c, Tree t, int G, const float *ll, const float *value, double Cpuct,
                                                             const double *logtab) {
   __shared__ WaveLds s;
@@ -2107,7 +2218,7 @@ __global__ void __launch_bounds__(64) k_expand_legal_select(DevCfg c, Tree t, in
   if (g >= G) return;
   (void)expand_legal_game<false>(s, c, t, g, g, ll, value, nullptr);
   __syncthreads();
-  select_game<OneLeaf, FPU>(s, c, t, g, Cpuct, logtab, true, ONE_LEAF);
+  select_game<OneLeaf, FPU, SOLVE>(s, c, t, g, Cpuct, logtab, true, ONE_LEAF);
 }
 
 // ================================================================================================
@@ -2137,7 +2248,7 @@ __global__ void __launch_bounds__(EXPAND_THREADS) k_expand_multi(DevCfg c, Tree 
   expand_game_multi<false>(s, c, t, G, g, kexp, logits, nullptr, stats, value, lp.VL);
 }
 
-template <bool FPU>
+template <bool FPU, bool SOLVE>
 __global__ void __launch_bounds__(EXPAND_THREADS) k_expand_select_multi(DevCfg c, Tree t, int G, int kexp, int ksel, LogitSrc logits,
                                                                         const float *stats, const float *value, double Cpuct,
                                                                         const double *logtab, LeafPar lp) {
@@ -2145,7 +2256,7 @@ __global__ void __launch_bounds__(EXPAND_THREADS) k_expand_select_multi(DevCfg c
   const int g = blockIdx.x;
   if (g >= G) return;
   expand_game_multi<false>(s, c, t, G, g, kexp, logits, nullptr, stats, value, lp.VL);
-  select_game_multi<FPU>(s, c, t, G, g, ksel, Cpuct, logtab, true, lp);
+  select_game_multi<FPU, SOLVE>(s, c, t, G, g, ksel, Cpuct, logtab, true, lp);
 }
 
 __global__ void __launch_bounds__(64) k_expand_legal_multi(DevCfg c, Tree t, int G, int kexp, const float *ll, const float *value, LeafPar lp) {
@@ -2155,14 +2266,14 @@ __global__ void __launch_bounds__(64) k_expand_legal_multi(DevCfg c, Tree t, int
   expand_game_multi<true>(s, c, t, G, g, kexp, LogitSrc{}, ll, nullptr, value, lp.VL);
 }
 
-template <bool FPU>
+template <bool FPU, bool SOLVE>
 __global__ void __launch_bounds__(64) k_expand_legal_select_multi(DevCfg c, Tree t, int G, int kexp, int ksel, const float *ll,
                                                                   const float *value, double Cpuct, const double *logtab, LeafPar lp) {
   __shared__ WaveLds s;
   const int g = blockIdx.x;
   if (g >= G) return;
   expand_game_multi<true>(s, c, t, G, g, kexp, LogitSrc{}, ll, nullptr, value, lp.VL);
-  select_game_multi<FPU>(s, c, t, G, g, ksel, Cpuct, logtab, true, lp);
+  select_game_multi<FPU, SOLVE>(s, c, t, G, g, ksel, Cpuct, logtab, true, lp);
 }
 
 // ================================================================================================
@@ -2194,6 +2305,9 @@ __global__ void __launch_bounds__(64) k_expand_legal_select_multi(DevCfg c, Tree
 // The new root's state is board slot 0: the child's board, or -- a child that was never selected (Q1: every child has
 // N = 1, so a sampled move can be one; under FPC_RULES_VISITS it has N = 0 and the game is a fresh root's) -- the old root's board with the move made, which is what a selection would
 // have done, and no more (no GetGameResult / legal-moves pass).
+// Proof statuses (fpc_search_set_solver; t.S null: none): every node that moves takes its status along, into the second
+// set's array, which the host zeroed before the launch -- so fresh rows, the root of a failed advance and every node created
+// later are unknown.
 // Root noise: a new root that is already expanded gets it here, child i (ascending flat order) from gamma[g][i], with
 // expand_finish's operations in expand_finish's order; an unexpanded one gets it when it is expanded (n == 0).
 // ================================================================================================
@@ -2240,6 +2354,7 @@ __global__ void __launch_bounds__(64) k_tree_advance(DevCfg c, Tree t, Tree o, i
   if (lane == 0) {
     o.N[nb] = rootN; o.W[nb] = r < 0 ? 0.0 : t.W[ob + r]; o.P[nb] = r < 0 ? 0.f : t.P[ob + r]; o.mv[nb] = 0xffff; o.parent[nb] = -1;
     o.child0[nb] = r < 0 ? -1 : t.child0[ob + r]; o.nch[nb] = r < 0 ? (uint16_t)0 : t.nch[ob + r]; o.bslot[nb] = 0;
+    if (t.S != nullptr && r >= 0) o.S[nb] = t.S[ob + r];      // (the host zeroed o.S: a failed advance's root and a fresh row stay 0)
   }
   // ---- its state -> board slot 0 (the root of a tree is always in slot 0)
   if (rslot < 0) {
@@ -2284,6 +2399,7 @@ __global__ void __launch_bounds__(64) k_tree_advance(DevCfg c, Tree t, Tree o, i
         dn = nb + tail + p;
         o.N[dn] = t.N[so]; o.W[dn] = t.W[so]; o.P[dn] = t.P[so]; o.mv[dn] = t.mv[so]; o.parent[dn] = head + en;
         o.child0[dn] = t.child0[so]; o.nch[dn] = t.nch[so];
+        if (t.S != nullptr) o.S[dn] = t.S[so];
         bs = t.bslot[so];
       }
       const unsigned long long mat = __ballot(bs >= 0);
@@ -2306,7 +2422,7 @@ __global__ void __launch_bounds__(64) k_tree_advance(DevCfg c, Tree t, Tree o, i
   }
   if (errbits & (ERR_CAP_NODES | ERR_CAP_BOARDS)) {         // leave a childless root rather than a half-built tree
     __syncthreads();
-    if (lane == 0) { o.child0[nb] = -1; o.nch[nb] = 0; }
+    if (lane == 0) { o.child0[nb] = -1; o.nch[nb] = 0; if (t.S != nullptr) o.S[nb] = FPC_PROOF_UNKNOWN; }
     tail = 1; nbo = 1;
     __syncthreads();
   }

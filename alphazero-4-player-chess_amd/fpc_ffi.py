@@ -19,6 +19,7 @@ REPLAY_RINGS, REPLAY_SCRATCH, REPLAY_COLLECTED, REPLAY_GATHERED = 2, 2, 0, 1    
 RULES_STRICT, RULES_PUCT, RULES_ROTATION, RULES_PLANES, RULES_FULL_MOVES, RULES_FIXED = 0, 1, 2, 4, 8, 15
 RULES_TERMINAL, RULES_TRAINING = 16, 31   # Q5 + the terminal value (search past terminal leaves, value by result); FIXED | TERMINAL
 RULES_VISITS, RULES_SELFPLAY = 32, 63     # Q1: N counts backups, every node is born with N = 0; TRAINING | VISITS
+PROOF_UNKNOWN, PROOF_WIN, PROOF_LOSS, PROOF_DRAW = 0, 1, 2, 3      # fpc_search_proofs: a node's status, from its own side to move
 FPU_ZERO, FPU_PARENT = 0, 1               # fpc_search_set_fpu: q of an unvisited child (PUCT): 0, or the parent's Q - reduction
 
 
@@ -164,6 +165,8 @@ _SIGS = {
     "fpc_search_set_leaves": (C.c_int, [C.c_void_p, C.c_int, C.c_double]),
     "fpc_search_set_live_rows": (C.c_int, [C.c_void_p, C.c_int]),
     "fpc_search_set_fpu": (C.c_int, [C.c_void_p, C.c_int, C.c_double]),
+    "fpc_search_set_solver": (C.c_int, [C.c_void_p, C.c_int]),
+    "fpc_search_proofs": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "fpc_tuples_reserve": (C.c_int, [C.c_void_p, C.c_int]),
     "fpc_tuples_reset": (C.c_int, [C.c_void_p]),
     "fpc_collect_tuples": (C.c_int, [C.c_void_p, P(C.c_int), C.c_int]),
@@ -652,6 +655,21 @@ class Engine:
         child with no visit, pending ones included, gets q = W_p / N_p - reduction of the node above it.  Persistent; without
         RULES_VISITS no child is ever unvisited and the setting has no effect."""
         self._chk(self.L.fpc_search_set_fpu(self.h, int(mode), float(reduction)))
+
+    def set_solver(self, on):
+        """MCTS solver (include/fpc_engine.h fpc_search_set_solver): terminal results are proven up the tree -- proven
+        children are backed up without a board, moves that lose are left out of the selection, a proven root idles, and
+        search_play plays a proven win or draw.  In effect only under RULES_PUCT | RULES_TERMINAL; persistent."""
+        self._chk(self.L.fpc_search_set_solver(self.h, int(on)))
+
+    def search_proofs(self, max_children=256):
+        """(root statuses uint8 [G], child statuses uint8 [G, max_children]) of the search: PROOF_* from each node's own
+        side to move, children in search_results' order (include/fpc_engine.h fpc_search_proofs)"""
+        G = self.G
+        root = np.zeros(G, np.uint8)
+        child = np.zeros((G, max_children), np.uint8)
+        self._chk(self.L.fpc_search_proofs(self.h, int(max_children), root.ctypes.data, child.ctypes.data))
+        return root, child
 
     def set_live_rows(self, on):
         """live-row numbering (include/fpc_engine.h fpc_search_set_live_rows): every step's live leaves are the network's

@@ -23,6 +23,10 @@ args["sim_budget"] = "per_game" | "visit_target" makes continue_search give ever
 (budgets_for) instead of the batch-wide one; search(games, budgets=...) / continue_search(..., budgets=...) take an
 explicit per-game list.  Absent / None: no budget is ever set.
 
+MCTS solver (opt-in; include/fpc_engine.h fpc_search_set_solver): args["solver"] = True proves wins, losses and draws in
+the tree under args["rules"] = "training" / "selfplay" -- a proven child is backed up without a board, a move that loses is
+left out of the selection, a proven root idles -- and fpc_search_play / selfplay.play(solver=True) play a proven win or draw.
+
 Live-row numbering (opt-in; include/fpc_engine.h fpc_search_set_live_rows): args["live_rows"] = True makes every step work
 on its live leaves only -- the same trees; the fused search's policy Linear computes ceil(live / 256) row tiles, and an
 external evaluator sees [n_live,24,R,R] (the live leaves in ascending row order) and returns n_live rows.
@@ -102,6 +106,9 @@ class MCTS:
         self.born = 0 if int(self.rules) & 32 else 1
         fpu = args.get("fpu", None) if hasattr(args, "get") else None
         self.fpu = None if fpu is None else float(fpu)
+        # args["solver"] = True (opt-in): the MCTS solver (fpc_search_set_solver) -- terminal results are proven up the tree;
+        # in effect only where the rule set holds RULES_PUCT and RULES_TERMINAL ("training", "selfplay"), inert elsewhere
+        self.solver = bool(args.get("solver", False)) if hasattr(args, "get") else False
         self.root_noise = bool(args.get("root_noise", False)) if hasattr(args, "get") else False
         self._noise_rng = np.random.default_rng(int(args.get("noise_seed", 0))) if self.root_noise else None
         self.leaves = int(args.get("leaves_per_step", 1)) if hasattr(args, "get") else 1
@@ -123,6 +130,9 @@ class MCTS:
             raise ValueError("sim_budget must be one of %r, not %r" % (SIM_BUDGET_MODES, self.sim_budget))
         # args["live_rows"] = True (opt-in): only the live leaves of a step are evaluated (fpc_search_set_live_rows)
         self.live_rows = bool(args.get("live_rows", False)) if hasattr(args, "get") else False
+
+    def solver_in_effect(self):
+        return self.solver and (int(self.rules) & 17) == 17       # RULES_PUCT | RULES_TERMINAL
 
     def _set_fpu(self, eng):
         if self.fpu is None:
@@ -175,6 +185,7 @@ class MCTS:
             eng.set_root_noise(None, 0.0)
         eng.search_begin(pods, float(self.args["C"]))
         eng.set_live_rows(self.live_rows)                  # as set_leaves; here, where no selection can be pending
+        eng.set_solver(self.solver)                        # the same; begin has cleared the statuses
         if budgets is not None:
             budgets = [int(b) for b in budgets]
             eng.search_set_budget(budgets)
@@ -228,6 +239,7 @@ class MCTS:
         else:
             kept = eng.search_advance(flats, keep_idx, roots=pods)
         eng.set_live_rows(self.live_rows)
+        eng.set_solver(self.solver)
         if budgets is None:
             budgets = budgets_for(kept, int(self.args["num_searches"]), eng.max_sims, self.sim_budget, self.born)
         if budgets is not None:

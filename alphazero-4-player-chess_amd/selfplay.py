@@ -35,16 +35,34 @@ def sample_action(flats, visits, temperature, u):
     return int(flats[min(k, len(flats) - 1)])
 
 
-def sample_move(flats, visits, temperature, u):
+def proven_pick(root_proof, child_proof):
+    """The solver's pick rule (include/fpc_engine.h fpc_search_set_solver): the index of the child a proven root plays -- the
+    first child with status LOSS under a root proven WIN, the first child with status DRAW under a root proven DRAW, at
+    every temperature -- or None where the draw decides (a root proven LOSS or unknown)."""
+    want = {fpc_ffi.PROOF_WIN: fpc_ffi.PROOF_LOSS, fpc_ffi.PROOF_DRAW: fpc_ffi.PROOF_DRAW}.get(int(root_proof))
+    if want is None or child_proof is None:
+        return None
+    for k, st in enumerate(child_proof):
+        if int(st) == want:
+            return k
+    return None
+
+
+def sample_move(flats, visits, temperature, u, root_proof=0, child_proof=None):
     """The draw of the device path (include/fpc_engine.h fpc_search_play) in plain Python -- the readable
     statement of that spec and the model the tests hold k_play_ply against.  Children in the tree's order:
       temperature > 0:  w_k = pow(N_k, 1 / temperature) (libm, f64); c_k = c_{k-1} + w_k strictly left to right;
                         x = u * S with S the last sum; the pick is the first k with c_k > x, else the last child;
       temperature == 0: the first child with the largest N.
       S == 0 (no child has a visit: fpc_ffi.RULES_VISITS only): child min(n - 1, int(u * n)).
+    root_proof / child_proof (the solver in effect: the statuses fpc_search_proofs reports for this root and its children):
+    a proven win or draw is played whatever the draw would say (proven_pick).
     Differs from sample_action only in rounding (f64 sums of unnormalised weights against f32 probabilities
     renormalised twice): the two pick the same child unless u * S lies within about 1e-5 * S of a c_k."""
     n = len(flats)
+    forced = proven_pick(root_proof, None if child_proof is None else child_proof[:n])
+    if forced is not None:
+        return int(flats[forced])
     if temperature == 0:
         best = 0
         for k in range(1, n):
@@ -79,7 +97,7 @@ class Episode:
 
 
 def play(search_fn, eng, start_boards, args, uniforms, continue_fn=None, on_searched=None, device_play=False, refill=None,
-         z_from_result=False):
+         z_from_result=False, solver=False):
     """search_fn(list_of_PODs) -> search_results dict (fpc_ffi.Engine.search_results layout) and
     leaves the PODs with the piece-list order the search produced.  uniforms[ply][gid] in [0,1): the draw of game gid at
     its OWN ply.
@@ -104,6 +122,9 @@ def play(search_fn, eng, start_boards, args, uniforms, continue_fn=None, on_sear
     labels its entries by r, as FPC_RULES_TERMINAL values a terminal leaf -- 0.0 for a stalemate, else +1.0 where the
     entry's side-to-move team is the winner (WIN_RY: team 0, WIN_BG: team 1) and -1.0 where it is not.  The
     max_game_length branch is untouched.
+    solver (opt-in, default False; the engine's solver must be in effect -- fpc_search_set_solver under RULES_PUCT |
+    RULES_TERMINAL): the host loop plays a root proven WIN or DRAW by proven_pick from eng.search_proofs(); a root proven
+    LOSS or unknown keeps sample_action's draw.  The device path needs no flag: fpc_search_play applies the same rule.
     Returns the list of finished Episodes (all games, in game-id order)."""
     states = [fpc_ffi.clone_board(b) for b in start_boards]
     ids = list(range(len(states)))
@@ -117,12 +138,14 @@ def play(search_fn, eng, start_boards, args, uniforms, continue_fn=None, on_sear
             on_searched(list(ids), step)
         plies = [eps[g].length for g in ids]                     # each game's own ply
         picks = []
+        proofs = eng.search_proofs() if solver and not device_play else None
         for i in range(len(states)):
             n = int(res["n_children"][i])
             flats, visits = res["flat"][i, :n].copy(), res["visits"][i, :n].copy()
             eps[ids[i]].entries.append((fpc_ffi.clone_board(states[i]), flats, visits))
             if not device_play:
-                picks.append(sample_action(flats, visits, T, uniforms[plies[i]][ids[i]]))
+                forced = None if proofs is None else proven_pick(proofs[0][i], proofs[1][i, :n])
+                picks.append(int(flats[forced]) if forced is not None else sample_action(flats, visits, T, uniforms[plies[i]][ids[i]]))
         if device_play:
             fl, results, pods = eng.search_play(T, [uniforms[p][g] for p, g in zip(plies, ids)])
             if int(fl.min()) < 0:

@@ -340,6 +340,55 @@ int fpc_search_set_budget(fpc_engine *e, const int *budget /* host [n_games], nu
  * FPC_EINVAL: null engine, `on` outside 0..1.  The first call with on = 1 allocates 4 * max_games + 1 ints. */
 int fpc_search_set_live_rows(fpc_engine *e, int on);
 
+/* ---- MCTS solver (opt-in; additions only, fpc_abi_version() unchanged; held against tests/solver_model.py) -------------
+ * FPC_RULES_TERMINAL lets a search go on past terminal leaves, but a terminal leaf reached again is materialised, judged
+ * and averaged into W / N again.  With the solver every node carries one byte of proof status, seen from the node's OWN
+ * side to move -- the frame of the terminal value v: */
+enum { FPC_PROOF_UNKNOWN = 0, FPC_PROOF_WIN = 1, FPC_PROOF_LOSS = 2, FPC_PROOF_DRAW = 3 };
+/* The proven value pv is +1 for WIN, -1 for LOSS, 0 for DRAW.  The proof is over the TREE's children: the legal moves whose
+ * prior was not flushed to exactly zero, judged by the engine's GetGameResult (Q13 included).
+ * The solver is IN EFFECT only while the switch is on and the rule set holds both FPC_RULES_PUCT and FPC_RULES_TERMINAL;
+ * under any other rule set the call is accepted and changes nothing (fpc_search_set_fpu's convention).  In effect, one
+ * descent of game g is today's except for:
+ *   1. proven root      a root that has children and a status other than 0: the row is dead and nothing is written --
+ *                       exactly a budget-idle row; the game stays alive, carries no error, sims_done does not move.  A
+ *                       childless root takes today's path, a terminal root leaves the search as ever.
+ *   2. excluded child   among the children of the node the descent stands on, a child with status WIN (the move that loses)
+ *                       is no candidate.  The argmax over the others is the arithmetic as it is: strict >, lowest index on
+ *                       ties, the FPU q0 unchanged.  No candidate gives FPC_ESELECT as ever (unreachable while (a) holds).
+ *   3. proven backup    a chosen child with a status other than 0 ends the descent: pv(status) is backed up from that node
+ *                       along the path, leaf first, sign alternating, N += 1 each; sims_done += 1; the row is dead, no
+ *                       pending visit is added and the game's selection of the step ends there -- the bookkeeping of a
+ *                       terminal backup, counted by budgets and max_sims the same way, without board materialisation,
+ *                       GetGameResult or move generation.  The check comes before the collision check.
+ *   4. marking          a descent that ends on an unknown leaf whose GetGameResult is not in progress makes today's terminal
+ *                       backup, then sets the leaf's status from v (+1 WIN, -1 LOSS, 0 DRAW) and propagates: with c the node
+ *                       just proven and p its parent, stop if there is no parent or p is proven already; if c is LOSS, p
+ *                       becomes WIN; otherwise stop if any child of p is unknown, else p becomes LOSS if all are WIN and
+ *                       DRAW if not; continue with p as c.  A status never changes once it is set.
+ * Invariants: (a) an unknown node with children has at least one unknown child; (b) a proven non-root node is never
+ * descended through; (c) under leaf-parallel search a proof ends the game's selection of the step, so no descent of the
+ * same step sees it and a proven node has VL == 0 when a descent reaches it -- rows of the same step that are pending below
+ * a node proven later are expanded and backed up as ever.
+ * Lifetime: fpc_search_begin clears the statuses; fpc_search_advance(_refill) carries them with the subtree (in the second
+ * tree set, beside N / W / P), fresh rows and the childless root of a failed advance get 0 -- whenever the arrays exist,
+ * switch on or off.  A new root that is proven and has children is idle from the first step; its kept_visits is as ever.
+ * fpc_search_play with the solver in effect: a root proven WIN plays its first child with status LOSS, a root proven DRAW
+ * its first child with status DRAW, at every temperature; a root proven LOSS or unknown takes today's draw.  Everything
+ * after the pick (the move, the result, next_out) is unchanged.
+ * Unchanged on purpose: fpc_collect_tuples stores the visit counts as they are, fpc_search_run does not end early when
+ * every row is idle.
+ * fpc_search_set_solver is persistent, like fpc_search_set_leaves, and follows fpc_search_set_live_rows' call-sequence
+ * rule.  FPC_ESTATE: a selection has been issued and the search's results have not been read.  FPC_EINVAL: null engine,
+ * `on` outside 0..1.  The first on = 1 allocates the status arrays (one byte per node; for both tree sets once the second
+ * exists), zeroed; FPC_ENOMEM if that fails. */
+int fpc_search_set_solver(fpc_engine *e, int on);
+/* The statuses of each root and of its children in the tree's child order (the order fpc_search_results reports), entries
+ * past a root's children 0.  Follows the rules of fpc_search_results (FPC_ESTATE before any fpc_search_begin, FPC_EINVAL
+ * for a negative max_children); does not finish a search.  All zero if the solver was never switched on. */
+int fpc_search_proofs(fpc_engine *e, int max_children, uint8_t *root_proof /* host [G] */,
+                      uint8_t *child_proof /* host [G][max_children], nullable */);
+
 /* ---- device-side move choice (opt-in): what a self-play ply does between the finished search and fpc_search_advance /
  * the next fpc_search_begin -- choose each game's move from the root's visit counts (alphazero.py:104-118), make it
  * (TakeAction, :119) and judge the game (GetGameResult, :120-123) -- as ONE launch (k_play_ply, one wave per game); the
