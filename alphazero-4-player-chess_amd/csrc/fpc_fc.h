@@ -55,7 +55,8 @@ constexpr int FC_LDS = 3 * FC_XBUF + 4 * FC_WRING;   // 163840: the whole LDS of
 
 // one 1-KiB LDS-DMA piece (64 lanes x 16 B): global (SGPR base + per-lane byte offset) -> LDS, no VGPR
 // destination.  Inline asm on purpose: every wait for these pieces is an explicit counted s_waitcnt in
-// k_fc.  M0 carries the wave-uniform LDS byte address and is restored inside the statement.
+// k_fc16.  M0 carries the wave-uniform LDS byte address and is restored inside the statement.  (k_fc16's form; k_fcw and
+// k_fcw8 own M0 and write it once per group of pieces: fcw_set_m0 below.)
 __device__ __forceinline__ void fc_dma(const void *gsrc_uniform, uint32_t lane_off, uint32_t lds_addr_uniform) {
   uint32_t keep;
   asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
@@ -70,12 +71,32 @@ __device__ __forceinline__ void fc_dma2_nt(const void *gsrc_uniform, uint32_t la
                "global_load_lds_dwordx4 %1, %2 offset:1024 nt\n\ts_mov_b32 m0, %0"
                : "=&s"(keep) : "v"(lane_off), "s"(gsrc_uniform), "s"(lds_addr_uniform) : "memory");
 }
-// the same with the non-temporal hint: for bytes that are read once per launch (the weight stream)
-__device__ __forceinline__ void fc_dma_nt(const void *gsrc_uniform, uint32_t lane_off, uint32_t lds_addr_uniform) {
-  uint32_t keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2 nt\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(lane_off), "s"(gsrc_uniform), "s"(lds_addr_uniform) : "memory");
+
+// k_fcw / k_fcw8: the kernel OWNS M0 from its first piece to its last -- no save, no restore (the compiler has no use
+// for M0 in these kernels: no other M0 in their ISA).  M0 is written once per GROUP of pieces that lie back to back in
+// LDS (fcw_set_m0: the group's LDS byte address + MID), and every piece of the group is one instruction whose immediate
+// I * 1024 - MID (within -4096 .. 3072) moves the LDS destination AND the global source: the caller's source address
+// (scalar base + per-lane offset) is the piece's own minus that immediate.
+__device__ __forceinline__ void fcw_set_m0(uint32_t lds_addr_uniform) {
+  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0" : : "s"(lds_addr_uniform) : "memory");
 }
+template <int OFF, bool NT>
+__device__ __forceinline__ void fcw_piece(const void *gsrc_uniform, uint32_t lane_off) {
+  static_assert(OFF >= -4096 && OFF <= 3072 && OFF % 1024 == 0, "a piece's immediate");
+  if (NT) asm volatile("global_load_lds_dwordx4 %0, %1 offset:%2 nt" : : "v"(lane_off), "s"(gsrc_uniform), "i"(OFF) : "memory");
+  else asm volatile("global_load_lds_dwordx4 %0, %1 offset:%2" : : "v"(lane_off), "s"(gsrc_uniform), "i"(OFF) : "memory");
+}
+// piece i of a group of N (i is a constant wherever this is called: the tile-row loops are unrolled)
+template <int MID, int N, bool NT, int I = 0>
+__device__ __forceinline__ void fcw_piece_at(int i, const void *gsrc_uniform, uint32_t lane_off) {
+  if constexpr (I < N) {
+    if (i == I) fcw_piece<I * 1024 - MID, NT>(gsrc_uniform, lane_off);
+    else fcw_piece_at<MID, N, NT, I + 1>(i, gsrc_uniform, lane_off);
+  }
+}
+constexpr int FCW_XMID = 4096;    // the 8 activation pieces of a wave and stage: immediates -4096 .. 3072
+constexpr int FCW_WMID = 3072;    // k_fcw: the 6 weight pieces of a k-step: -3072 .. 2048
+constexpr int FCW8_WMID = 1024;   // k_fcw8: the 3 weight pieces of a k-step: -1024 .. 1024
 
 // ------------------------------------------------------------------------------------------------------------
 // k_fc16: the Linear on v_mfma_f32_16x16x32 (the shape the chip holds the higher clock on under load,
@@ -230,7 +251,18 @@ __global__ void __launch_bounds__(FC_THREADS, 1) k_fc16(FcArgs g) {
 // = 160 KiB.  The activations therefore run ONE stage ahead and the weights two; vmcnt retires in issue order, so
 // within a stage the activation pieces go out FIRST (k-step 0, tile rows 0..7) and the weight pieces behind them:
 // waiting for the youngest activation piece then leaves the twelve weight pieces issued behind it in flight.
-// Issue pattern per stage and wave: k-step 0: 8 X pieces, then 3 weight pairs; k-step 1: 3 weight pairs.  Counted waits:
+// Issue pattern per stage and wave: k-step 0: 8 X pieces (behind tile rows 0..7), then 3 weight pairs (rows 8, 10, 12);
+// k-step 1: 3 weight pairs (rows 2, 6, 10).  The 20 pieces are three GROUPS, each contiguous in LDS, each behind ONE write
+// of M0 (fcw_set_m0 + fcw_piece_at above; the kernel owns M0, nothing saves or restores it):
+//   X  -- the wave's 64 rows of the next stage, 8 KiB; M0 = its middle, immediates -4096 .. 3072.  In memory the eight
+//         pieces are 8 rows (8 * Kp * 2 bytes) apart, not 1 KiB: piece p's scalar base carries p * (8 * Kp * 2 - 1024),
+//         strength-reduced by the compiler to eight loop-invariant SGPR pairs + the stage offset (no VGPR more: 206 + 256);
+//   W0 -- the six tiles of k-step 0 two stages ahead, 6 KiB of the ring and 6 KiB of the weight stream, both advancing by
+//         1 KiB per tile: one base, M0 = middle, immediates -3072 .. 2048;
+//   W1 -- the same for k-step 1 (the source a k-step of wk32 bytes further on).
+// 3 M0 writes per stage where the per-statement form had 28 (save, set, restore per statement; an s_mov to M0 beside the
+// fragment stream waits for the wave's LDS reads in flight).  Piece count, order and tile rows are unchanged, so the
+// counted waits are:
 //   start of k-step (s, 0): the weights of (s, 1), issued in (s - 2, 1); behind them a whole stage       -> vmcnt(20)
 //   start of k-step (s, 1): the weights of (s + 1, 0), issued in (s - 1, 0); behind them 6 + 8 + 6       -> vmcnt(20)
 //   k-step (s, 1) behind tile row 13: the activations of stage s + 1, issued in (s, 0); behind them 6 + 6 -> vmcnt(12),
@@ -292,15 +324,21 @@ __global__ void __launch_bounds__(FC_THREADS, 1) k_fcw(FcArgs g) {
   const std::integral_constant<int, 0> c0{};
   const std::integral_constant<int, 1> c1{};
 
-  auto issue_x = [&](int s, int p) {              // piece p (8 rows) of activation stage s
+  // Group X: M0 = the middle of the wave's 8 KiB of stage s; piece p (8 rows) lands at M0 + (p * 1024 - FCW_XMID) and
+  // comes from the scalar base + the same immediate: the base carries p * xpiece minus that immediate
+  auto m0_x = [&](int s) { fcw_set_m0((uint32_t)__builtin_amdgcn_readfirstlane((s & 1) * FC_XBUF + wave * 64 * 128 + FCW_XMID)); };
+  auto issue_x = [&](int s, int p) {              // piece p of activation stage s
     const int sc = s < S ? s : S - 1;
-    fc_dma(xbase + (long)p * xpiece + (long)sc * 128, xlane[p & 1],
-           (uint32_t)__builtin_amdgcn_readfirstlane((s & 1) * FC_XBUF + (wave * 64 + p * 8) * 128));
+    fcw_piece_at<FCW_XMID, 8, false>(p, xbase + (long)p * (xpiece - 1024) + FCW_XMID + (long)sc * 128, xlane[p & 1]);
   };
+  // Groups W0 / W1: M0 = the middle of the six tiles of k32-step j of stage s in the ring; source and ring both advance
+  // by 1 KiB per tile, so one base (+ FCW_WMID) serves the six pieces
+  auto m0_w = [&](int s, int j) { fcw_set_m0((uint32_t)__builtin_amdgcn_readfirstlane(lds_w + ((s & 1) * 12 + j * 6) * 1024 + FCW_WMID)); };
   auto issue_w2 = [&](int s, int j, int n0) {      // column tiles n0, n0 + 1 of k32-step j of stage s
     const int sc = s < S ? s : S - 1;
-    fc_dma2_nt(wbase + (long)(2 * sc + j) * wk32 + n0 * 1024, wlane,
-               (uint32_t)__builtin_amdgcn_readfirstlane(lds_w + ((s & 1) * 12 + j * 6 + n0) * 1024));
+    const unsigned char *src = wbase + (long)(2 * sc + j) * wk32 + FCW_WMID;
+    fcw_piece_at<FCW_WMID, 6, true>(n0, src, wlane);
+    fcw_piece_at<FCW_WMID, 6, true>(n0 + 1, src, wlane);
   };
   auto xfrag = [&](int slot, int t, const unsigned char *ab, int j) {
     xr[slot] = *reinterpret_cast<const u32x4_t *>(ab + lds_off<64>(t * 16 + (lane & 15), j * 4 + (lane >> 4)));
@@ -330,20 +368,24 @@ __global__ void __launch_bounds__(FC_THREADS, 1) k_fcw(FcArgs g) {
       if (J == 1 && t == 13) { asm volatile("s_waitcnt vmcnt(12)" ::: "memory"); __syncthreads(); }
       if (t + 3 < 16) xfrag((t + 3) & 3, t + 3, ab, J);
       else xfrag((t + 3) & 3, t + 3 - 16, abn, NXT);
+      if (J == 0 && t == 0) m0_x(s + 1);
       if (J == 0 && t < 8) issue_x(s + 1, t);
+      if (J == 0 && t == 8) m0_w(s + 2, 0);
       if (J == 0 && (t == 8 || t == 10 || t == 12)) issue_w2(s + 2, 0, t - 8);
+      if (J == 1 && t == 2) m0_w(s + 2, 1);
       if (J == 1 && (t == 2 || t == 6 || t == 10)) issue_w2(s + 2, 1, (t - 2) / 2);
       __builtin_amdgcn_sched_barrier(0);
     }
   };
 
   // prologue: the activations of stage 0, the weights of stages 0 and 1, then the first fragments
+  m0_x(0);
 #pragma unroll
   for (int p = 0; p < 8; ++p) issue_x(0, p);
 #pragma unroll
   for (int st = 0; st < 2; ++st)
 #pragma unroll
-    for (int j = 0; j < 2; ++j) { issue_w2(st, j, 0); issue_w2(st, j, 2); issue_w2(st, j, 4); }
+    for (int j = 0; j < 2; ++j) { m0_w(st, j); issue_w2(st, j, 0); issue_w2(st, j, 2); issue_w2(st, j, 4); }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
 #pragma unroll
@@ -404,7 +446,8 @@ __global__ void __launch_bounds__(FC_THREADS, 1) k_fcw(FcArgs g) {
 // Schedule: k_fcw's.  Two activation stages (64 KiB) + a 12 KiB ring per wave (2 stages x 2 k-steps x 3 pieces) =
 // 112 KiB of LDS; the 48 KiB this frees are NOT spent (a deeper ring only behind a same-box A/B).  Issue pattern per
 // stage and wave: k-step 0: 8 X pieces (tile rows 0..7), then 3 weight pieces (rows 8, 10, 12); k-step 1: 3 weight pieces
-// (rows 2, 6, 10).  Counted waits, derived as k_fcw's:
+// (rows 2, 6, 10) -- k_fcw's three groups behind one M0 write each, a weight group being the 3 KiB of a k-step's three
+// pair pieces (M0 = the second piece, immediates -1024 .. 1024).  Counted waits, derived as k_fcw's:
 //   start of k-step (s, 0): the weights of (s, 1), issued in (s - 2, 1); behind them stage s - 1: 8 + 3 + 3   -> vmcnt(14)
 //   start of k-step (s, 1): the weights of (s + 1, 0), issued in (s - 1, 0); behind them 3 + 8 + 3             -> vmcnt(14)
 //   k-step (s, 1) behind tile row 13: the activations of stage s + 1, issued in (s, 0); behind them 3 + 3      -> vmcnt(6),
@@ -470,15 +513,16 @@ __global__ void __launch_bounds__(FC_THREADS, 1) k_fcw8(Fc8Args g8) {
   const std::integral_constant<int, 0> c0{};
   const std::integral_constant<int, 1> c1{};
 
+  // the groups and their M0 as in k_fcw; a weight group is the three pair pieces of a k-step
+  auto m0_x = [&](int s) { fcw_set_m0((uint32_t)__builtin_amdgcn_readfirstlane((s & 1) * FC_XBUF + wave * 64 * 128 + FCW_XMID)); };
   auto issue_x = [&](int s, int p) {              // piece p (8 rows) of activation stage s
     const int sc = s < S ? s : S - 1;
-    fc_dma(xbase + (long)p * xpiece + (long)sc * 128, xlane[p & 1],
-           (uint32_t)__builtin_amdgcn_readfirstlane((s & 1) * FC_XBUF + (wave * 64 + p * 8) * 128));
+    fcw_piece_at<FCW_XMID, 8, false>(p, xbase + (long)p * (xpiece - 1024) + FCW_XMID + (long)sc * 128, xlane[p & 1]);
   };
+  auto m0_w = [&](int s, int j) { fcw_set_m0((uint32_t)__builtin_amdgcn_readfirstlane(lds_w + ((s & 1) * 6 + j * 3) * 1024 + FCW8_WMID)); };
   auto issue_w = [&](int s, int j, int p) {        // column pair p of k32-step j of stage s
     const int sc = s < S ? s : S - 1;
-    fc_dma_nt(wbase + (long)(2 * sc + j) * wk32 + p * 1024, wlane,
-              (uint32_t)__builtin_amdgcn_readfirstlane(lds_w + ((s & 1) * 6 + j * 3 + p) * 1024));
+    fcw_piece_at<FCW8_WMID, 3, true>(p, wbase + (long)(2 * sc + j) * wk32 + FCW8_WMID, wlane);
   };
   auto xfrag = [&](int slot, int t, const unsigned char *ab, int j) {
     xr[slot] = *reinterpret_cast<const u32x4_t *>(ab + lds_off<64>(t * 16 + (lane & 15), j * 4 + (lane >> 4)));
@@ -516,20 +560,24 @@ __global__ void __launch_bounds__(FC_THREADS, 1) k_fcw8(Fc8Args g8) {
       if (t + 3 < 16) xfrag((t + 3) & 3, t + 3, ab, J);
       else xfrag((t + 3) & 3, t + 3 - 16, abn, NXT);
       if (t == 1 || t == 3 || t == 5) wcvt(NXT, (t - 1) / 2);
+      if (J == 0 && t == 0) m0_x(s + 1);
       if (J == 0 && t < 8) issue_x(s + 1, t);
+      if (J == 0 && t == 8) m0_w(s + 2, 0);
       if (J == 0 && (t == 8 || t == 10 || t == 12)) issue_w(s + 2, 0, (t - 8) / 2);
+      if (J == 1 && t == 2) m0_w(s + 2, 1);
       if (J == 1 && (t == 2 || t == 6 || t == 10)) issue_w(s + 2, 1, (t - 2) / 4);
       __builtin_amdgcn_sched_barrier(0);
     }
   };
 
   // prologue: the activations of stage 0, the weights of stages 0 and 1, then the first fragments
+  m0_x(0);
 #pragma unroll
   for (int p = 0; p < 8; ++p) issue_x(0, p);
 #pragma unroll
   for (int st = 0; st < 2; ++st)
 #pragma unroll
-    for (int j = 0; j < 2; ++j) { issue_w(st, j, 0); issue_w(st, j, 1); issue_w(st, j, 2); }
+    for (int j = 0; j < 2; ++j) { m0_w(st, j); issue_w(st, j, 0); issue_w(st, j, 1); issue_w(st, j, 2); }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
 #pragma unroll
@@ -585,10 +633,19 @@ __global__ void __launch_bounds__(256) k_fc_reduce(const float *part, const floa
     const int j = gw == 256 ? q >> 6 : (q * 4) / gw;    // column group of gw columns (256: k_fc / k_fc16; 384: k_fcw)
     const int col = q * 4 - j * gw;
     const int base = j < G1 ? j * s1 : G1 * s1 + (j - G1) * s2, cnt = j < G1 ? s1 : s2;
+    // logit_at's shape: the bias and all of the group's slab quads (at most LOGIT_MAX_SLABS = 2 * FC_SPLITK, plan_fc)
+    // are requested before the first is added -- one memory round trip per thread, not 1 + cnt dependent ones (a
+    // run-time trip count, one load and a full wait per trip, held the kernel at latency x concurrency: 5.2 TB/s
+    // of slabs that k_fcw wrote microseconds earlier).  The additions and their order are what they were.
+    float4 p[LOGIT_MAX_SLABS];
+#pragma unroll
+    for (int k = 0; k < LOGIT_MAX_SLABS; ++k)
+      p[k] = k < cnt ? *reinterpret_cast<const float4 *>(part + ((long)(base + k) * Mtot + m) * gw + col) : float4{0.f, 0.f, 0.f, 0.f};
     v = *reinterpret_cast<const float4 *>(bias + q * 4);
-    for (int k = 0; k < cnt; ++k) {
-      const float4 p = *reinterpret_cast<const float4 *>(part + ((long)(base + k) * Mtot + m) * gw + col);
-      v.x += p.x; v.y += p.y; v.z += p.z; v.w += p.w;
+#pragma unroll
+    for (int k = 0; k < LOGIT_MAX_SLABS; ++k) {
+      v.x = k < cnt ? v.x + p[k].x : v.x; v.y = k < cnt ? v.y + p[k].y : v.y;
+      v.z = k < cnt ? v.z + p[k].z : v.z; v.w = k < cnt ? v.w + p[k].w : v.w;
     }
     if (logits) *reinterpret_cast<float4 *>(logits + (long)m * A + q * 4) = v;     // null: the fused search keeps only the records
   }
