@@ -32,6 +32,9 @@ num_searches simulations have gone through it, kept ones included, and needs a h
 solver (default False; with rules = "training" / "selfplay") -- the MCTS solver (fpc_search_set_solver): the search proves
 wins, losses and draws up the tree, and play() plays a proven win or draw at every temperature -- on the host path from
 fpc_search_proofs (selfplay.proven_pick), on the device_play path inside fpc_search_play.  arena.py does not use it.
+forced_playouts (default None; a float, usually 2.0, with rules = "selfplay" and root_noise) -- forced playouts and policy
+target pruning at the root (fpc_search_set_forced): the tuples and the move draw take the pruned visit counts, on the host
+path from fpc_search_targets (selfplay.play(targets=True)), on the device paths inside fpc_collect_tuples / fpc_search_play.
 z_from_result (default False: the reference's labels, quirk Q12) -- a game that ends on the board labels its tuples by the
 result (winner's team +1, the other -1, stalemate 0), the value rules = "training" backs up from a terminal leaf.
 """
@@ -126,7 +129,7 @@ class AlphaZero:
                                  on_searched=on_searched if self.device_replay else None, device_play=device_play,
                                  refill=[g._b for g in games[G:]] if total > G else None,
                                  z_from_result=bool(self.args.get("z_from_result", False)) if hasattr(self.args, "get") else False,
-                                 solver=self.mcts.solver_in_effect())
+                                 solver=self.mcts.solver_in_effect(), targets=self.mcts.forced_in_effect())
         split = self.args["replay_buffer_capacity"] / (self.args["replay_buffer_capacity"] + self.args["validation_buffer_capacity"])
         if self.device_replay:
             z_team = np.zeros((2, len(episodes)), np.float32)      # z by (game, team of the side to move), as the Episodes have it

@@ -88,6 +88,9 @@ struct fpc_engine {
                                   // from then on whatever the switch says: cleared by begin, carried by an advance
   uint8_t *d_proof = nullptr;     // fpc_search_proofs' staging: [G] roots | [G][max_children] children
   size_t proof_cap = 0;
+  // ---- forced playouts and target pruning (fpc_search_set_forced): the factor is t.forced
+  int *d_target = nullptr;        // fpc_search_targets' staging: [G][max_children]
+  size_t target_cap = 0;
   // ---- device-side move choice (fpc_search_play); allocated on the first call
   double *d_powtab = nullptr;     // [max_sims + 16] pow(v, 1 / powtab_T) by the host libm
   double powtab_T = -1.0;         // temperature the uploaded table was made for (-1: none yet)
@@ -598,16 +601,29 @@ static bool solving(const fpc_engine *e) {
   return e->solver && e->t.S != nullptr && (e->dc.rules & need) == need;
 }
 
-// every selecting kernel exists without and with first-play urgency (fpc_search_set_fpu) and without and with the solver
-// (fpc_search_set_solver): the instance the settings ask for
-#define FPC_LAUNCH_SELECT(kernel, e, ...)                         \
+// forced playouts and target pruning are in effect: the factor is > 0 and the rule set holds both FPC_RULES_PUCT and
+// FPC_RULES_VISITS
+static bool forcing(const fpc_engine *e) {
+  const int need = FPC_RULES_PUCT | FPC_RULES_VISITS;
+  return e->t.forced > 0.0 && (e->dc.rules & need) == need;
+}
+
+// every selecting kernel exists without and with first-play urgency (fpc_search_set_fpu), without and with the solver
+// (fpc_search_set_solver) and without and with forced playouts (fpc_search_set_forced): the instance the settings ask for.
+// With forcing not in effect these are the four <*, *, false> instances, chosen as before.
+#define FPC_LAUNCH_SELECT_F(kernel, e, FORCE, ...)                \
   do {                                                            \
     const bool fpu_ = (e)->t.fpu_mode != FPC_FPU_ZERO;            \
     if (solving(e)) {                                             \
-      if (fpu_) FPC_LAUNCH((kernel<true, true>), __VA_ARGS__);      \
-      else FPC_LAUNCH((kernel<false, true>), __VA_ARGS__);          \
-    } else if (fpu_) FPC_LAUNCH((kernel<true, false>), __VA_ARGS__); \
-    else FPC_LAUNCH((kernel<false, false>), __VA_ARGS__);           \
+      if (fpu_) FPC_LAUNCH((kernel<true, true, FORCE>), __VA_ARGS__);      \
+      else FPC_LAUNCH((kernel<false, true, FORCE>), __VA_ARGS__);          \
+    } else if (fpu_) FPC_LAUNCH((kernel<true, false, FORCE>), __VA_ARGS__); \
+    else FPC_LAUNCH((kernel<false, false, FORCE>), __VA_ARGS__);           \
+  } while (0)
+#define FPC_LAUNCH_SELECT(kernel, e, ...)                         \
+  do {                                                            \
+    if (forcing(e)) FPC_LAUNCH_SELECT_F(kernel, e, true, __VA_ARGS__); \
+    else FPC_LAUNCH_SELECT_F(kernel, e, false, __VA_ARGS__);      \
   } while (0)
 
 // k leaves per game (k_select_multi), or one (k_select) in a one-leaf search
@@ -867,6 +883,40 @@ int fpc_search_proofs(fpc_engine *e, int max_children, uint8_t *root_proof, uint
   HIPCHK(e, hipGetLastError());
   HIPCHK(e, hipMemcpyAsync(root_proof, d_out, (size_t)G, hipMemcpyDeviceToHost, e->stream));
   if (child_proof && nch) HIPCHK(e, hipMemcpyAsync(child_proof, d_out + G, nch, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(e, hipStreamSynchronize(e->stream));
+  return 0;
+}
+
+int fpc_search_set_forced(fpc_engine *e, double factor) {
+  if (!e) return fail(e, FPC_EINVAL, "null engine");
+  if (!std::isfinite(factor) || factor < 0.0) return fail(e, FPC_EINVAL, "fpc_search_set_forced: factor must be finite and >= 0");
+  if (e->searching && e->selected && e->stepping)
+    return fail(e, FPC_ESTATE, "fpc_search_set_forced: a selection has been issued and the search's results have not been read");
+  e->t.forced = factor;           // read by the FORCE instances and by root_targets; t2 is only ever a set of arrays
+  return 0;
+}
+
+int fpc_search_targets(fpc_engine *e, int max_children, int *child_target) {
+  if (!e || !e->searching) return fail(e, FPC_ESTATE, "fpc_search_begin has not been called");
+  if (max_children < 0 || !child_target) return fail(e, FPC_EINVAL, "fpc_search_targets: bad max_children or null child_target");
+  USE_DEV(e);
+  const int G = e->G;
+  const size_t nch = (size_t)G * max_children;
+  if (!nch) return 0;
+  int r;
+  if (nch > e->target_cap) {
+    if (e->d_target) {
+      (void)hipFree(e->d_target);
+      e->allocs.erase(std::find(e->allocs.begin(), e->allocs.end(), (void *)e->d_target));
+      e->d_target = nullptr;
+    }
+    e->target_cap = 0;
+    if ((r = dalloc(e, &e->d_target, nch))) return r;
+    e->target_cap = nch;
+  }
+  FPC_LAUNCH(k_root_targets, G, 64, e->stream, e->t, G, max_children, e->Cpuct, forcing(e) ? 1 : 0, e->d_target);
+  HIPCHK(e, hipGetLastError());
+  HIPCHK(e, hipMemcpyAsync(child_target, e->d_target, nch * sizeof(int), hipMemcpyDeviceToHost, e->stream));
   HIPCHK(e, hipStreamSynchronize(e->stream));
   return 0;
 }
@@ -1144,7 +1194,7 @@ int fpc_search_play(fpc_engine *e, double temperature, const double *uniform, in
       if (!ev) HIPCHK(e, hipEventCreate(&ev));
   if (timed) HIPCHK(e, hipEventRecord(e->play_ev[0], e->stream));
   FPC_LAUNCH(k_play_ply, G, 64, e->stream, e->dc, e->t, G, (const double *)e->d_powtab, (int)ntab, argmax ? 1 : 0,
-             (const double *)e->d_play_u, solving(e) ? 1 : 0, d_flat, d_res, e->d_play_next, d_err);
+             (const double *)e->d_play_u, solving(e) ? 1 : 0, e->Cpuct, forcing(e) ? 1 : 0, d_flat, d_res, e->d_play_next, d_err);
   HIPCHK(e, hipGetLastError());
   if (timed) HIPCHK(e, hipEventRecord(e->play_ev[1], e->stream));
   std::vector<int> errs(G);
@@ -1215,7 +1265,8 @@ int fpc_collect_tuples(fpc_engine *e, const int *game_id, int ply) {
   const int G = e->G;
   if (e->tuple_count + G > e->tuple_cap) return fail(e, FPC_ECAPACITY, "tuple buffer full (%d + %d > %d): fpc_tuples_reserve", e->tuple_count, G, e->tuple_cap);
   if (game_id) HIPCHK(e, hipMemcpyAsync(e->d_tgame, game_id, (size_t)G * sizeof(int), hipMemcpyHostToDevice, e->stream));
-  FPC_LAUNCH(k_collect_tuples, G, 64, e->stream, e->t, G, game_id ? (const int *)e->d_tgame : (const int *)nullptr, ply, e->d_tuples + e->tuple_count);
+  FPC_LAUNCH(k_collect_tuples, G, 64, e->stream, e->t, G, game_id ? (const int *)e->d_tgame : (const int *)nullptr, ply, e->Cpuct,
+             forcing(e) ? 1 : 0, e->d_tuples + e->tuple_count);
   HIPCHK(e, hipGetLastError());
   if (game_id) HIPCHK(e, hipStreamSynchronize(e->stream));     // the caller may reuse game_id
   e->tuple_count += G;

@@ -96,6 +96,9 @@ struct Tree {
   // k_tree_advance, read by k_play_ply and k_root_proofs.  Nothing gives a node a birth status: the host zeroes the array
   // (fpc_search_begin, the destination set of an advance), and a status is only ever stored on a node that exists.
   uint8_t *S;
+  // forced playouts and policy target pruning at the root (fpc_search_set_forced; 0: off): the factor k.  Read by the FORCE
+  // instances of the selecting kernels at the root level only, and by root_targets.  Last in the struct: no other field moves.
+  double forced;
 };
 __host__ __forceinline__ int born_visits(int rules) { return (rules & FPC_RULES_VISITS) ? 0 : 1; }
 
@@ -276,7 +279,8 @@ __device__ __forceinline__ int wave_list_erase_append(uint8_t *list, int len, in
 // Wave-cooperative and wave-uniform: every lane derives the same scalars from the LDS board, the piece
 // lists are edited one entry per lane, lane 0 writes the scalars.  All lanes must call.
 // INSTANCE: 0 the one-leaf kernels, 1 the leaf-parallel selection, 2 k_tree_advance, 3 k_play_ply, 4 / 5 the descents of
-// 0 / 1 with first-play urgency on, 8 / 9 / 12 / 13 those four with the solver in effect -- separate
+// 0 / 1 with first-play urgency on, 8 / 9 / 12 / 13 those four with the solver in effect, + 16 those eight with forced
+// playouts in effect -- separate
 // instances, so that the one-leaf kernels' callees -- and with them the compiler's inlining decisions and the kernels'
 // ISA -- stay exactly what they were before leaf-parallel search and subtree reuse
 template <int INSTANCE = 0>
@@ -1235,8 +1239,66 @@ __global__ void __launch_bounds__(64) k_root_proofs(Tree t, int G, int maxc, uin
   if (lane == 0) root_proof[g] = t.S[nb];
 }
 
-// training tuples (alphazero.py:104-112): root mailbox + side to move + sparse pi of a finished search
-__global__ void __launch_bounds__(64) k_collect_tuples(Tree t, int G, const int *game_id, int ply, fpc_tuple *out) {
+// Policy target pruning (fpc_search_set_forced; the numeric spec is in include/fpc_engine.h and DESIGN 5.11): the pruned
+// visit counts T_k of the children c0 .. c0 + nc - 1 of game nb's root, from the STORED statistics, f64 as written.  All 64
+// lanes call; sink(k, T_k) is called once for every k < nc by the lane that owns child k (k % 64).  b, the first child with
+// the largest N, is the only thing found across lanes (a ballot per pass of 64 and a scalar lane read); each lane then
+// walks its own child's count down, at most sqrt(factor * max_sims) trips.  Reads the tree and writes nothing into it.
+template <class Sink>
+__device__ __forceinline__ void root_targets(const Tree &t, size_t nb, int c0, int nc, double Cpuct, Sink &&sink) {
+  const int lane = lane_id();
+  int b = -1, Nb = 0;
+  for (int base = 0; base < nc; base += 64) {
+    const int k = base + lane;
+    const int Nk = k < nc ? t.N[nb + c0 + k] : -1;
+    int cur = 0, top = wave_read(Nk, 0);       // lane 0 of a pass always owns a child
+    for (;;) {                                 // the first lane with the pass's largest N, select_game's way
+      const unsigned long long gt = __ballot(Nk > top);
+      if (!gt) break;
+      cur = (int)__ffsll((long long)gt) - 1;
+      top = wave_read(Nk, cur);
+    }
+    if (b < 0 || top > Nb) { b = base + cur; Nb = top; }
+  }
+  if (b < 0) return;                           // no children
+  const int Np = t.N[nb];
+  const double sq = sqrt((double)Np);
+  double ub = 0.0;
+  if (Nb > 0) ub = -(t.W[nb + c0 + b] / (double)Nb) + Cpuct * (double)t.P[nb + c0 + b] * sq / (double)(1 + Nb);
+  for (int k = lane; k < nc; k += 64) {
+    const int Nk = t.N[nb + c0 + k];
+    int T = Nk;
+    if (Nb > 0 && k != b && Nk > 0) {
+      const double Pk = (double)t.P[nb + c0 + k];
+      const int F = (int)sqrt(t.forced * Pk * (double)Np);
+      const double q = -(t.W[nb + c0 + k] / (double)Nk), a = Cpuct * Pk * sq;
+      for (int f = 0; f < F; ++f) {
+        if (T == 0 || q + a / (double)T >= ub) break;
+        T = T - 1;
+      }
+      if (T < Nk && T <= 1) T = 0;             // a child reduced to a single playout is pruned outright
+    }
+    sink(k, T);
+  }
+}
+
+// fpc_search_targets: the pruned visit counts of each root's children in the tree's child order (prune == 0, forcing not
+// in effect: the stored counts), entries past a root's children 0
+__global__ void __launch_bounds__(64) k_root_targets(Tree t, int G, int maxc, double Cpuct, int prune, int *target) {
+  const int g = blockIdx.x;
+  if (g >= G) return;
+  const int lane = lane_id();
+  const size_t nb = (size_t)g * t.node_cap;
+  const int c0 = t.child0[nb], nc = c0 < 0 ? 0 : (int)t.nch[nb];
+  int *out = target + (size_t)g * maxc;
+  for (int k = lane; k < maxc; k += 64) out[k] = k < nc ? t.N[nb + c0 + k] : 0;
+  // the same lane owns child k in both loops: its second store follows its first
+  if (prune) root_targets(t, nb, c0, nc, Cpuct, [&](int k, int T) { if (k < maxc) out[k] = T; });
+}
+
+// training tuples (alphazero.py:104-112): root mailbox + side to move + sparse pi of a finished search.
+// prune != 0 (forced playouts are in effect): the pruned counts T_k stand where the visit counts N_k stand.
+__global__ void __launch_bounds__(64) k_collect_tuples(Tree t, int G, const int *game_id, int ply, double Cpuct, int prune, fpc_tuple *out) {
   const int g = blockIdx.x;
   if (g >= G) return;
   const int lane = lane_id();
@@ -1250,6 +1312,8 @@ __global__ void __launch_bounds__(64) k_collect_tuples(Tree t, int G, const int 
     rec->flat[k] = in ? t.mv[nb + c0 + k] : (uint16_t)0;
     rec->visits[k] = in ? (uint16_t)t.N[nb + c0 + k] : (uint16_t)0;
   }
+  // the same lane owns child k in both loops: its second store follows its first
+  if (prune) root_targets(t, nb, c0, nc, Cpuct, [&](int k, int T) { if (k < FPC_TUPLE_MAXC) rec->visits[k] = (uint16_t)T; });
   if (lane < 44) rec->pad1[lane] = 0;
   if (lane == 0) {
     rec->turn = root->turn; rec->pad0 = 0;
@@ -1283,8 +1347,10 @@ __global__ void __launch_bounds__(256) k_tuples_set_z(fpc_tuple *recs, int count
 // ================================================================================================
 // solve != 0 (the solver is in effect): a root proven WIN plays its first child with status LOSS, a root proven DRAW its
 // first child with status DRAW, at every temperature; a root proven LOSS or unknown takes the draw above.
+// prune != 0 (forced playouts are in effect): the draw is from the pruned counts T_k (root_targets) instead of N_k.
 __global__ void __launch_bounds__(64) k_play_ply(DevCfg c, Tree t, int G, const double *powtab, int powtab_n, int argmax,
-                                                 const double *uniform, int solve, int *flat, int *result, fpc_board *next, int *err) {
+                                                 const double *uniform, int solve, double Cpuct, int prune, int *flat, int *result,
+                                                 fpc_board *next, int *err) {
   __shared__ WaveLds s;
   __shared__ double wt[FPC_MAX_MOVES];
   const int g = blockIdx.x;
@@ -1302,6 +1368,9 @@ __global__ void __launch_bounds__(64) k_play_ply(DevCfg c, Tree t, int G, const 
     if (lane == 0) { flat[g] = -1; result[g] = -1; err[g] = 0; }
     return;
   }
+  if (prune) {                                       // wave-uniform; T_k <= N_k, the clamp as below
+    root_targets(t, nb, c0, nc, Cpuct, [&](int k, int n) { wt[k] = argmax ? (double)n : powtab[n < 0 ? 0 : n < powtab_n ? n : powtab_n - 1]; });
+  } else
   for (int base = 0; base < nc; base += 64) {
     const int k = base + lane;
     if (k < nc) {
@@ -1546,7 +1615,11 @@ struct LeafRow {         // ... and for descent k of a leaf-parallel step
 //      ends the game's selection of the step -- before the collision check;
 //   4. an unknown leaf whose game is over: the terminal backup, then the leaf's status from the value backed up and the
 //      proof's way up (prove_upward).
-template <class M, bool FPU, bool SOLVE, bool MULTI = !std::is_same<M, OneLeaf>::value>
+// FORCE: forced playouts are in effect (fpc_search_set_forced under FPC_RULES_PUCT | FPC_RULES_VISITS), a third
+// switch of the same kind: every selecting kernel exists as <FPU, SOLVE, FORCE> in eight instances, and the <*, *, false>
+// ones neither load the factor nor test for the root level.  At the root level (n == 0) a child with 0 < N' < sqrt(factor *
+// P * N'_root) gets u = +infinity; the argmax, the solver's exclusion and everything after the choice are unchanged.
+template <class M, bool FPU, bool SOLVE, bool FORCE, bool MULTI = !std::is_same<M, OneLeaf>::value>
 __device__ inline void select_game(WaveLds &s, const DevCfg &c, const Tree &t, int g, double Cpuct, const double *logtab, bool to_next, M *m) {
 #define FPC_ROW (MULTI ? m->k * m->G + g : g)     // the leaf's row (folded to g for one leaf per game)
   const int lane = lane_id();
@@ -1637,6 +1710,9 @@ __device__ inline void select_game(WaveLds &s, const DevCfg &c, const Tree &t, i
           // AlphaZero PUCT, the child's value seen from the parent: -W/N + C P sqrt(N_parent) / (1 + N)
           const double q = Nc > 0 ? -(Wc / (double)Nc) : q0;
           u = q + Cpuct * Pc * sqrtNp / (double)(1 + Nc);
+          if constexpr (FORCE) {                     // in effect only under FPC_RULES_PUCT: this branch
+            if (n == 0 && Nc > 0 && (double)Nc < sqrt(t.forced * Pc * (double)Nn)) u = __builtin_inf();
+          }
         } else {
           const double q = Nc > 0 ? Wc / (double)Nc : 0.0;
           const double e = Cpuct * sqrt(L / (double)(1 + Nc));
@@ -1718,7 +1794,7 @@ __device__ inline void select_game(WaveLds &s, const DevCfg &c, const Tree &t, i
     lds_load_board(&s, &pool[parent_slot]);
     int from;
     const int to = flat_to(c, leaf_mv, &from);
-    const bool moved = make_move_wave<MULTI + (FPU ? 4 : 0) + (SOLVE ? 8 : 0)>(&s.b, from, to, c);
+    const bool moved = make_move_wave<MULTI + (FPU ? 4 : 0) + (SOLVE ? 8 : 0) + (FORCE ? 16 : 0)>(&s.b, from, to, c);
     if (lane == 0) {
       int e = moved ? 0 : ERR_MOVE;
       int ns = nboards0;                     // fetched with the root's fields; only this block ever changes it
@@ -1739,7 +1815,7 @@ __device__ inline void select_game(WaveLds &s, const DevCfg &c, const Tree &t, i
   FPC_TS(6);
   // ---- GetGameResult (node.cpp:28-29) then, if in progress, GetLegalMoves
   //      (four_player_chess_board.py:38) on the same state, with their list reorderings
-  wave_position_ops<MULTI + (FPU ? 4 : 0) + (SOLVE ? 8 : 0)>(&s, c, true, true, -1);
+  wave_position_ops<MULTI + (FPU ? 4 : 0) + (SOLVE ? 8 : 0) + (FORCE ? 16 : 0)>(&s, c, true, true, -1);
   FPC_TS(12);
   lds_store_board(&s, &t.boards[(size_t)g * t.board_cap + slot]);
   const int res = s.result;
@@ -1787,13 +1863,13 @@ constexpr OneLeaf *ONE_LEAF = nullptr;
 // K descents of one game in one step (leaf-parallel search): row k*G + g for k = 0, 1, ...  The first row that is not
 // live (collision, terminal leaf, dead game, the game's budget reached) ends the game's selection for this step; its
 // remaining rows are dead.  With the solver a proven root and a backup from a proven child end it the same way.
-template <bool FPU, bool SOLVE>
+template <bool FPU, bool SOLVE, bool FORCE>
 __device__ inline void select_game_multi(WaveLds &s, const DevCfg &c, const Tree &t, int G, int g, int K, double Cpuct,
                                          const double *logtab, bool to_next, const LeafPar &lp) {
   int k = 0;
   while (k < K) {
     LeafRow r{lp, k, G, false, 0, 0, 0};
-    select_game<LeafRow, FPU, SOLVE>(s, c, t, g, Cpuct, logtab, to_next, &r);
+    select_game<LeafRow, FPU, SOLVE, FORCE>(s, c, t, g, Cpuct, logtab, to_next, &r);
     ++k;
     if (!r.live) break;
     __syncthreads();                         // this descent's tree stores (VL, bslot, nboards, board) precede the next one
@@ -1804,20 +1880,20 @@ __device__ inline void select_game_multi(WaveLds &s, const DevCfg &c, const Tree
     for (; k < K; ++k) { leaf_node[k * G + g] = -1; leaf_slot[k * G + g] = -1; }
 }
 
-template <bool FPU, bool SOLVE>
+template <bool FPU, bool SOLVE, bool FORCE>
 __global__ void __launch_bounds__(64) k_select(DevCfg c, Tree t, int G, double Cpuct, const double *logtab) {
   __shared__ WaveLds s;
   const int g = blockIdx.x;
   if (g >= G) return;
-  select_game<OneLeaf, FPU, SOLVE>(s, c, t, g, Cpuct, logtab, false, ONE_LEAF);
+  select_game<OneLeaf, FPU, SOLVE, FORCE>(s, c, t, g, Cpuct, logtab, false, ONE_LEAF);
 }
 
-template <bool FPU, bool SOLVE>
+template <bool FPU, bool SOLVE, bool FORCE>
 __global__ void __launch_bounds__(64) k_select_multi(DevCfg c, Tree t, int G, int K, double Cpuct, const double *logtab, LeafPar lp) {
   __shared__ WaveLds s;
   const int g = blockIdx.x;
   if (g >= G) return;
-  select_game_multi<FPU, SOLVE>(s, c, t, G, g, K, Cpuct, logtab, false, lp);
+  select_game_multi<FPU, SOLVE, FORCE>(s, c, t, G, g, K, Cpuct, logtab, false, lp);
 }
 
 // pending-visit counters of the roots (node storage, and with it VL, is reused across searches; children are zeroed
@@ -2155,7 +2231,7 @@ __global__ void __launch_bounds__(EXPAND_THREADS) k_expand(DevCfg c, Tree t, int
 // dependent-kernel gap less per step).  Other blocks may still be expanding step s when this block's
 // selection publishes its leaf, and strict mode reads the turn of the batch's FIRST live leaf across games
 // (Q6), so the selection writes the _nx leaf arrays; the host swaps them in after the launch.
-template <bool FPU, bool SOLVE>
+template <bool FPU, bool SOLVE, bool FORCE>
 __global__ void __launch_bounds__(EXPAND_THREADS) k_expand_select(DevCfg c, Tree t, int G, LogitSrc logits, const float *stats,
                                                                   const float *value, double Cpuct, const double *logtab) {
   __shared__ WaveLds s;
@@ -2165,7 +2241,7 @@ __global__ void __launch_bounds__(EXPAND_THREADS) k_expand_select(DevCfg c, Tree
   (void)expand_game<false>(s, c, t, G, g, g, logits, stats, value, nullptr);
   __syncthreads();                           // the new children (global stores of other lanes) are visible to the descent
   FPC_TS(4);
-  select_game<OneLeaf, FPU, SOLVE>(s, c, t, g, Cpuct, logtab, true, ONE_LEAF);
+  select_game<OneLeaf, FPU, SOLVE, FORCE>(s, c, t, g, Cpuct, logtab, true, ONE_LEAF);
 }
 
 
@@ -2210,7 +2286,7 @@ __global__ void __launch_bounds__(64) k_expand_legal(DevCfg c, Tree t, int G, co
 }
 
 // the legal-only head's counterpart of k_expand_select
-template <bool FPU, bool SOLVE>
+template <bool FPU, bool SOLVE, bool FORCE>
 __global__ void __launch_bounds__(64) k_expand_legal_select(DevCfg c, Tree t, int G, const float *ll, const float *value, double Cpuct,
                                                             const double *logtab) {
   __shared__ WaveLds s;
@@ -2218,7 +2294,7 @@ __global__ void __launch_bounds__(64) k_expand_legal_select(DevCfg c, Tree t, in
   if (g >= G) return;
   (void)expand_legal_game<false>(s, c, t, g, g, ll, value, nullptr);
   __syncthreads();
-  select_game<OneLeaf, FPU, SOLVE>(s, c, t, g, Cpuct, logtab, true, ONE_LEAF);
+  select_game<OneLeaf, FPU, SOLVE, FORCE>(s, c, t, g, Cpuct, logtab, true, ONE_LEAF);
 }
 
 // ================================================================================================
@@ -2248,7 +2324,7 @@ __global__ void __launch_bounds__(EXPAND_THREADS) k_expand_multi(DevCfg c, Tree 
   expand_game_multi<false>(s, c, t, G, g, kexp, logits, nullptr, stats, value, lp.VL);
 }
 
-template <bool FPU, bool SOLVE>
+template <bool FPU, bool SOLVE, bool FORCE>
 __global__ void __launch_bounds__(EXPAND_THREADS) k_expand_select_multi(DevCfg c, Tree t, int G, int kexp, int ksel, LogitSrc logits,
                                                                         const float *stats, const float *value, double Cpuct,
                                                                         const double *logtab, LeafPar lp) {
@@ -2256,7 +2332,7 @@ __global__ void __launch_bounds__(EXPAND_THREADS) k_expand_select_multi(DevCfg c
   const int g = blockIdx.x;
   if (g >= G) return;
   expand_game_multi<false>(s, c, t, G, g, kexp, logits, nullptr, stats, value, lp.VL);
-  select_game_multi<FPU, SOLVE>(s, c, t, G, g, ksel, Cpuct, logtab, true, lp);
+  select_game_multi<FPU, SOLVE, FORCE>(s, c, t, G, g, ksel, Cpuct, logtab, true, lp);
 }
 
 __global__ void __launch_bounds__(64) k_expand_legal_multi(DevCfg c, Tree t, int G, int kexp, const float *ll, const float *value, LeafPar lp) {
@@ -2266,14 +2342,14 @@ __global__ void __launch_bounds__(64) k_expand_legal_multi(DevCfg c, Tree t, int
   expand_game_multi<true>(s, c, t, G, g, kexp, LogitSrc{}, ll, nullptr, value, lp.VL);
 }
 
-template <bool FPU, bool SOLVE>
+template <bool FPU, bool SOLVE, bool FORCE>
 __global__ void __launch_bounds__(64) k_expand_legal_select_multi(DevCfg c, Tree t, int G, int kexp, int ksel, const float *ll,
                                                                   const float *value, double Cpuct, const double *logtab, LeafPar lp) {
   __shared__ WaveLds s;
   const int g = blockIdx.x;
   if (g >= G) return;
   expand_game_multi<true>(s, c, t, G, g, kexp, LogitSrc{}, ll, nullptr, value, lp.VL);
-  select_game_multi<FPU, SOLVE>(s, c, t, G, g, ksel, Cpuct, logtab, true, lp);
+  select_game_multi<FPU, SOLVE, FORCE>(s, c, t, G, g, ksel, Cpuct, logtab, true, lp);
 }
 
 // ================================================================================================

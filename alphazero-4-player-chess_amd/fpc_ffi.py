@@ -167,6 +167,8 @@ _SIGS = {
     "fpc_search_set_fpu": (C.c_int, [C.c_void_p, C.c_int, C.c_double]),
     "fpc_search_set_solver": (C.c_int, [C.c_void_p, C.c_int]),
     "fpc_search_proofs": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "fpc_search_set_forced": (C.c_int, [C.c_void_p, C.c_double]),
+    "fpc_search_targets": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "fpc_tuples_reserve": (C.c_int, [C.c_void_p, C.c_int]),
     "fpc_tuples_reset": (C.c_int, [C.c_void_p]),
     "fpc_collect_tuples": (C.c_int, [C.c_void_p, P(C.c_int), C.c_int]),
@@ -670,6 +672,20 @@ class Engine:
         child = np.zeros((G, max_children), np.uint8)
         self._chk(self.L.fpc_search_proofs(self.h, int(max_children), root.ctypes.data, child.ctypes.data))
         return root, child
+
+    def set_forced(self, factor):
+        """forced playouts and policy target pruning at the root (include/fpc_engine.h fpc_search_set_forced): a visited
+        root child is guaranteed sqrt(factor * P * N) simulations, and collect_tuples / search_play / search_targets take the
+        visits that only the forcing put there out again.  0: off (default); 2.0 is the usual value.  In effect only under
+        RULES_PUCT | RULES_VISITS; persistent."""
+        self._chk(self.L.fpc_search_set_forced(self.h, float(factor)))
+
+    def search_targets(self, max_children=256):
+        """int32 [G, max_children]: the pruned visit counts of each root's children in search_results' order, zero past a
+        root's children; the stored visit counts when forcing is not in effect (include/fpc_engine.h fpc_search_targets)"""
+        out = np.zeros((self.G, max_children), np.int32)
+        self._chk(self.L.fpc_search_targets(self.h, int(max_children), out.ctypes.data))
+        return out
 
     def set_live_rows(self, on):
         """live-row numbering (include/fpc_engine.h fpc_search_set_live_rows): every step's live leaves are the network's

@@ -27,6 +27,11 @@ MCTS solver (opt-in; include/fpc_engine.h fpc_search_set_solver): args["solver"]
 the tree under args["rules"] = "training" / "selfplay" -- a proven child is backed up without a board, a move that loses is
 left out of the selection, a proven root idles -- and fpc_search_play / selfplay.play(solver=True) play a proven win or draw.
 
+Forced playouts and policy target pruning (opt-in; include/fpc_engine.h fpc_search_set_forced): args["forced_playouts"] =
+None (default) | float, usually 2.0 -- with args["root_noise"] under args["rules"] = "selfplay" a visited root child is
+guaranteed sqrt(k * P * N) simulations, and the policy target (fpc_collect_tuples, fpc_search_play, fpc_search_targets /
+selfplay.play(targets=True)) leaves out the visits that only the forcing put there.
+
 Live-row numbering (opt-in; include/fpc_engine.h fpc_search_set_live_rows): args["live_rows"] = True makes every step work
 on its live leaves only -- the same trees; the fused search's policy Linear computes ceil(live / 256) row tiles, and an
 external evaluator sees [n_live,24,R,R] (the live leaves in ascending row order) and returns n_live rows.
@@ -109,6 +114,10 @@ class MCTS:
         # args["solver"] = True (opt-in): the MCTS solver (fpc_search_set_solver) -- terminal results are proven up the tree;
         # in effect only where the rule set holds RULES_PUCT and RULES_TERMINAL ("training", "selfplay"), inert elsewhere
         self.solver = bool(args.get("solver", False)) if hasattr(args, "get") else False
+        # args["forced_playouts"] = None (default) | float, usually 2.0 (opt-in): forced playouts and policy target pruning at
+        # the root (fpc_search_set_forced); in effect only where the rule set holds RULES_PUCT and RULES_VISITS ("selfplay")
+        forced = args.get("forced_playouts", None) if hasattr(args, "get") else None
+        self.forced = 0.0 if forced is None else float(forced)
         self.root_noise = bool(args.get("root_noise", False)) if hasattr(args, "get") else False
         self._noise_rng = np.random.default_rng(int(args.get("noise_seed", 0))) if self.root_noise else None
         self.leaves = int(args.get("leaves_per_step", 1)) if hasattr(args, "get") else 1
@@ -133,6 +142,9 @@ class MCTS:
 
     def solver_in_effect(self):
         return self.solver and (int(self.rules) & 17) == 17       # RULES_PUCT | RULES_TERMINAL
+
+    def forced_in_effect(self):
+        return self.forced > 0 and (int(self.rules) & 33) == 33   # RULES_PUCT | RULES_VISITS
 
     def _set_fpu(self, eng):
         if self.fpu is None:
@@ -186,6 +198,7 @@ class MCTS:
         eng.search_begin(pods, float(self.args["C"]))
         eng.set_live_rows(self.live_rows)                  # as set_leaves; here, where no selection can be pending
         eng.set_solver(self.solver)                        # the same; begin has cleared the statuses
+        eng.set_forced(self.forced)
         if budgets is not None:
             budgets = [int(b) for b in budgets]
             eng.search_set_budget(budgets)
@@ -240,6 +253,7 @@ class MCTS:
             kept = eng.search_advance(flats, keep_idx, roots=pods)
         eng.set_live_rows(self.live_rows)
         eng.set_solver(self.solver)
+        eng.set_forced(self.forced)
         if budgets is None:
             budgets = budgets_for(kept, int(self.args["num_searches"]), eng.max_sims, self.sim_budget, self.born)
         if budgets is not None:

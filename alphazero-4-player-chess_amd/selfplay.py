@@ -97,7 +97,7 @@ class Episode:
 
 
 def play(search_fn, eng, start_boards, args, uniforms, continue_fn=None, on_searched=None, device_play=False, refill=None,
-         z_from_result=False, solver=False):
+         z_from_result=False, solver=False, targets=False):
     """search_fn(list_of_PODs) -> search_results dict (fpc_ffi.Engine.search_results layout) and
     leaves the PODs with the piece-list order the search produced.  uniforms[ply][gid] in [0,1): the draw of game gid at
     its OWN ply.
@@ -125,6 +125,9 @@ def play(search_fn, eng, start_boards, args, uniforms, continue_fn=None, on_sear
     solver (opt-in, default False; the engine's solver must be in effect -- fpc_search_set_solver under RULES_PUCT |
     RULES_TERMINAL): the host loop plays a root proven WIN or DRAW by proven_pick from eng.search_proofs(); a root proven
     LOSS or unknown keeps sample_action's draw.  The device path needs no flag: fpc_search_play applies the same rule.
+    targets (opt-in, default False; the engine's forced playouts must be in effect -- fpc_search_set_forced under RULES_PUCT
+    | RULES_VISITS): Episode.entries hold the pruned visit counts of eng.search_targets() instead of the raw visits, and the
+    host loop draws its move from them.  The device path's draw needs no flag: fpc_search_play draws from the same counts.
     Returns the list of finished Episodes (all games, in game-id order)."""
     states = [fpc_ffi.clone_board(b) for b in start_boards]
     ids = list(range(len(states)))
@@ -139,9 +142,10 @@ def play(search_fn, eng, start_boards, args, uniforms, continue_fn=None, on_sear
         plies = [eps[g].length for g in ids]                     # each game's own ply
         picks = []
         proofs = eng.search_proofs() if solver and not device_play else None
+        counts = eng.search_targets(res["visits"].shape[1]) if targets else res["visits"]
         for i in range(len(states)):
             n = int(res["n_children"][i])
-            flats, visits = res["flat"][i, :n].copy(), res["visits"][i, :n].copy()
+            flats, visits = res["flat"][i, :n].copy(), counts[i, :n].copy()
             eps[ids[i]].entries.append((fpc_ffi.clone_board(states[i]), flats, visits))
             if not device_play:
                 forced = None if proofs is None else proven_pick(proofs[0][i], proofs[1][i, :n])

@@ -389,6 +389,53 @@ int fpc_search_set_solver(fpc_engine *e, int on);
 int fpc_search_proofs(fpc_engine *e, int max_children, uint8_t *root_proof /* host [G] */,
                       uint8_t *child_proof /* host [G][max_children], nullable */);
 
+/* ---- forced playouts and policy target pruning at the root (opt-in; additions only, fpc_abi_version() unchanged; held
+ * against tests/forced_model.py) ----------------------------------------------------------------------------------------
+ * Root Dirichlet noise (fpc_search_set_root_noise) distorts the training target twice: a noised move gets too few
+ * simulations to show that it is good, or it gets simulations that PUCT alone would never have spent and that go straight
+ * into the visit counts.  KataGo's pair: a visited root child is guaranteed sqrt(factor * P * N) simulations, and when the
+ * target is read the visits that only the forcing put there are taken out again.  Both are root-only, need no per-node
+ * state and are computed from the stored statistics.
+ * factor == 0: off (the default).  factor > 0: both, with that k (KataGo uses 2).  IN EFFECT only while the factor is > 0
+ * and the rule set holds both FPC_RULES_PUCT and FPC_RULES_VISITS (without FPC_RULES_VISITS every child is born with N = 1
+ * and "has been visited" means nothing); under any other rule set the call is accepted and changes nothing
+ * (fpc_search_set_fpu's convention).
+ * SELECTION, in effect, at the ROOT level of a descent only (the node the descent stands on is node 0).  For child i with
+ * effective count N' = N + VL, prior P (f32) and the root's effective count Nn (the value sqrtNp is made from):
+ *     nf_i = sqrt(factor * (double)P_i * (double)Nn)          f64, as written
+ *     if (N'_i > 0 && (double)N'_i < nf_i)  u_i = +infinity
+ * Everything else is the arithmetic as it is: strict >, the lowest index wins, also across the passes of 64 children, so
+ * among several forced children the first is taken.  A child with N' == 0 is never forced (FPU and q = 0 decide it as
+ * ever).  A child the solver excludes (status WIN) stays excluded even if forced; a forced child that is proven ends the
+ * descent with a proven backup, as any chosen proven child does.  A forced descent is an ordinary simulation for budgets,
+ * max_sims, virtual loss, collisions and terminal backups.  Below the root nothing changes.
+ * TARGET, per game, from the root's STORED N_p and its children's stored N_k, W_k, P_k (k in tree order) and the search's
+ * c_puct as C; f64 throughout, no contraction, evaluated as written:
+ *     b  = first k with the largest N_k;   T_b = N_b;   if N_b == 0: T_k = N_k for all k, done
+ *     sq = sqrt((double)N_p)
+ *     ub = -(W_b / (double)N_b) + C * (double)P_b * sq / (double)(1 + N_b)
+ *     for k != b:  T = N_k
+ *       if N_k > 0:
+ *         F = (int)sqrt(factor * (double)P_k * (double)N_p)
+ *         q = -(W_k / (double)N_k);   a = C * (double)P_k * sq
+ *         repeat at most F times:  if T == 0 or q + a / (double)T >= ub: stop;  T = T - 1
+ *             (u of the child at count T - 1 with q held fixed; 1 + (T - 1) == T)
+ *         if T < N_k and T <= 1: T = 0            (a child reduced to a single playout is pruned outright)
+ *       T_k = T
+ * CONSUMERS, in effect: fpc_collect_tuples stores T_k where it stores N_k; fpc_search_play draws from powtab[T_k] (the
+ * argmax is unchanged in outcome: T_b = N_b is still the first largest) and the solver's pick still overrides the draw;
+ * fpc_search_results and fpc_search_grandchildren keep reporting the stored counts.  The target is computed when it is
+ * read: nothing is written into the tree.
+ * fpc_search_set_forced is persistent, like fpc_search_set_leaves, and follows fpc_search_set_live_rows' call-sequence
+ * rule.  FPC_ESTATE: a selection has been issued and the search's results have not been read.  FPC_EINVAL (no state
+ * changed): null engine, a factor that is negative or not finite. */
+int fpc_search_set_forced(fpc_engine *e, double factor);
+/* The pruned visit counts T_k of each root's children in the tree's child order (the order fpc_search_results reports),
+ * entries past a root's children 0; the stored visit counts when forcing is not in effect.  Follows the rules of
+ * fpc_search_results (FPC_ESTATE before any fpc_search_begin, FPC_EINVAL for a negative max_children); does not finish a
+ * search. */
+int fpc_search_targets(fpc_engine *e, int max_children, int *child_target /* host [G][max_children] */);
+
 /* ---- device-side move choice (opt-in): what a self-play ply does between the finished search and fpc_search_advance /
  * the next fpc_search_begin -- choose each game's move from the root's visit counts (alphazero.py:104-118), make it
  * (TakeAction, :119) and judge the game (GetGameResult, :120-123) -- as ONE launch (k_play_ply, one wave per game); the
