@@ -35,6 +35,11 @@ fpc_search_proofs (selfplay.proven_pick), on the device_play path inside fpc_sea
 forced_playouts (default None; a float, usually 2.0, with rules = "selfplay" and root_noise) -- forced playouts and policy
 target pruning at the root (fpc_search_set_forced): the tuples and the move draw take the pruned visit counts, on the host
 path from fpc_search_targets (selfplay.play(targets=True)), on the device paths inside fpc_collect_tuples / fpc_search_play.
+playout_cap (default None; {"full_prob": p, "fast_searches": n, "record_fast": False}) -- playout cap randomization
+(fpc_search_set_fast_rows): every ply every game draws a full search (probability p) or a fast one of n simulations without
+noise, forcing or pruning.  record_fast False (the KataGo paper's way): a fast ply goes into neither buffer.  record_fast
+True: it is stored with policy-loss weight 0 (the record's FPC_TUPLE_FAST flag on the device path, a fifth item element on
+the host path) and _loss averages the policy cross-entropy over the full plies only; the value loss takes every row.
 z_from_result (default False: the reference's labels, quirk Q12) -- a game that ends on the board labels its tuples by the
 result (winner's team +1, the other -1, stalemate 0), the value rules = "training" backs up from a terminal leaf.
 """
@@ -67,6 +72,9 @@ class AlphaZero:
             self.experience_buffer = ReplayBuffer(args["replay_buffer_capacity"])
             self.validation_buffer = ReplayBuffer(args["validation_buffer_capacity"])
         self.gen = torch.Generator().manual_seed(seed) if seed is not None else None
+        cap = args.get("playout_cap", None) if hasattr(args, "get") else None
+        self.playout_cap = None if cap is None else {"full_prob": self.mcts.playout_cap[0], "fast_searches": self.mcts.playout_cap[1]}
+        self.record_fast = bool(cap.get("record_fast", False)) if hasattr(cap, "get") else False
         self.history = []
 
     # ---- self-play (alphazero.py:81-178) ----
@@ -97,10 +105,12 @@ class AlphaZero:
         eng = self._engine()
         L = int(self.args["max_game_length"])
         uniforms = torch.rand(L, total, generator=self.gen, dtype=torch.float64).tolist()
+        # the cap's draws are a second block, made only when the cap is on: a seeded run without it is what it was
+        cap_uniforms = torch.rand(L, total, generator=self.gen, dtype=torch.float64).tolist() if self.playout_cap is not None else None
 
-        def search_fn(pods):
+        def search_fn(pods, fast=None):
             boards = [self.gameType._wrap(p) for p in pods]
-            roots = self.mcts.search(boards)
+            roots = self.mcts.search(boards, fast=fast)
             arrs = [r.child_arrays() for r in roots]                 # no Python object per child
             n = max(len(f) for f, _ in arrs)
             res = {"n_children": np.array([len(f) for f, _ in arrs]),
@@ -110,8 +120,8 @@ class AlphaZero:
                 res["visits"][i, :len(v)] = v
             return res
 
-        def continue_fn(keep_idx, picks, pods):
-            return self.mcts.continue_search(pods, keep_idx, picks)
+        def continue_fn(keep_idx, picks, pods, fast=None):
+            return self.mcts.continue_search(pods, keep_idx, picks, fast=fast)
 
         where = {}                                        # device replay: (game id, loop step) -> index of the collected tuple
 
@@ -129,7 +139,8 @@ class AlphaZero:
                                  on_searched=on_searched if self.device_replay else None, device_play=device_play,
                                  refill=[g._b for g in games[G:]] if total > G else None,
                                  z_from_result=bool(self.args.get("z_from_result", False)) if hasattr(self.args, "get") else False,
-                                 solver=self.mcts.solver_in_effect(), targets=self.mcts.forced_in_effect())
+                                 solver=self.mcts.solver_in_effect(), targets=self.mcts.forced_in_effect(),
+                                 playout_cap=self.playout_cap, cap_uniforms=cap_uniforms)
         split = self.args["replay_buffer_capacity"] / (self.args["replay_buffer_capacity"] + self.args["validation_buffer_capacity"])
         if self.device_replay:
             z_team = np.zeros((2, len(episodes)), np.float32)      # z by (game, team of the side to move), as the Episodes have it
@@ -137,6 +148,8 @@ class AlphaZero:
             for k, ep in enumerate(episodes):
                 for ply, ((pod, _, _), z) in enumerate(zip(ep.entries, ep.z)):
                     z_team[pod.turn & 1, k] = z
+                    if ep.fast[ply] and not self.record_fast:     # a fast ply is not stored: no index, no split draw
+                        continue
                     src.append(where[(ep.gid, ep.start + ply)])
                     ring_of.append(0 if torch.rand(1, generator=self.gen).item() < split else 1)
             for k in range(0, len(episodes), eng.max_games):      # fpc_tuples_set_z takes max_games games per call
@@ -144,9 +157,14 @@ class AlphaZero:
             eng.replay_push(src_index=src, ring_of=ring_of)
             return episodes
         for ep in episodes:                               # handle_terminal_state, alphazero.py:53-78
-            for (pod, flats, visits), z in zip(ep.entries, ep.z):
+            for (pod, flats, visits), z, fast in zip(ep.entries, ep.z, ep.fast):
+                if fast and not self.record_fast:             # a fast ply is not stored: no split draw
+                    continue
                 buf = self.experience_buffer if torch.rand(1, generator=self.gen).item() < split else self.validation_buffer
-                buf.add((pod, flats, visits, float(z)))
+                if self.record_fast:
+                    buf.add((pod, flats, visits, float(z), 0.0 if fast else 1.0))
+                else:
+                    buf.add((pod, flats, visits, float(z)))
         return episodes
 
     # ---- optimiser step (alphazero.py:181-258) ----
@@ -158,15 +176,28 @@ class AlphaZero:
         A = self.gameType.action_space_size
         dev = next(self.model.parameters()).device
         # GetEncodedState(entry.state) encodes each tuple on its own => per-sample rotation (alphazero.py:71-73)
-        x = np.concatenate([eng.encode([pod]) for pod, _, _, _ in sample])
-        pi = torch.stack([tuples.dense_pi({"flat": np.asarray(f, np.int64), "visits": np.asarray(v, np.int64)}, A) for _, f, v, _ in sample])
+        x = np.concatenate([eng.encode([s[0]]) for s in sample])
+        pi = torch.stack([tuples.dense_pi({"flat": np.asarray(s[1], np.int64), "visits": np.asarray(s[2], np.int64)}, A) for s in sample])
         z = torch.tensor([s[3] for s in sample], dtype=torch.float32).view(-1, 1)
+        if self.record_fast:
+            w = torch.tensor([s[4] for s in sample], dtype=torch.float32).view(-1, 1)
+            return torch.from_numpy(x).to(dev), pi.to(dev), z.to(dev), w.to(dev)
         return torch.from_numpy(x).to(dev), pi.to(dev), z.to(dev)
 
+    def _sample(self, buf, bs):
+        """a minibatch of `buf`; with record_fast the device buffer decodes the weight column too"""
+        return buf.sample(bs, weights=True) if self.device_replay and self.record_fast else buf.sample(bs)
+
     def _loss(self, sample):
-        x, pi, z = self._batch(sample)
+        batch = self._batch(sample)
+        x, pi, z = batch[:3]
         out_policy, out_value = self.model(x)
-        policy_loss = F.cross_entropy(out_policy, pi)
+        if self.record_fast:      # sum_i w_i CE_i / max(sum_i w_i, 1): the policy loss of the full plies alone
+            w = batch[3].view(-1)
+            ce = F.cross_entropy(out_policy, pi, reduction="none")
+            policy_loss = (w * ce).sum() / torch.clamp(w.sum(), min=1.0)
+        else:
+            policy_loss = F.cross_entropy(out_policy, pi)
         value_loss = F.mse_loss(out_value.squeeze(), z.squeeze())
         return policy_loss, value_loss
 
@@ -176,7 +207,7 @@ class AlphaZero:
             return None
         last = None
         for _ in range(0, len(self.experience_buffer), bs):
-            policy_loss, value_loss = self._loss(self.experience_buffer.sample(bs))
+            policy_loss, value_loss = self._loss(self._sample(self.experience_buffer, bs))
             loss = policy_loss + value_loss
             self.optimizer.zero_grad()
             loss.backward()
@@ -191,7 +222,7 @@ class AlphaZero:
         bs = int(self.args["batch_size"])
         if len(self.validation_buffer) < bs:
             return None
-        policy_loss, value_loss = self._loss(self.validation_buffer.sample(bs))
+        policy_loss, value_loss = self._loss(self._sample(self.validation_buffer, bs))
         return {"policy_loss": policy_loss.item(), "value_loss": value_loss.item(), "loss": (policy_loss + value_loss).item()}
 
     def learn(self):                                      # alphazero.py:260-277

@@ -77,6 +77,8 @@ struct fpc_engine {
   std::vector<fpc_board> fresh_stage;  // their host staging (the entries at kept positions are not read from the caller)
   // ---- per-game simulation budgets (fpc_search_set_budget)
   int *d_budget = nullptr;        // [max_games], allocated on the first call; t.budget points here while budgets are set
+  // ---- playout cap randomization (fpc_search_set_fast_rows)
+  uint8_t *d_fast = nullptr;      // [max_games] padded to whole words, allocated on the first call; t.fast points here while a mask is set
   std::vector<int> base;          // [G] simulations already through each root: kept_visits - born_visits after an advance, else 0
   bool selected = false;          // a selection has been issued since the last begin / advance
   // ---- live-row numbering (fpc_search_set_live_rows)
@@ -562,6 +564,7 @@ int fpc_search_begin(fpc_engine *e, const fpc_board *roots, int n_games, double 
   e->sims_issued = 0;
   e->base.assign((size_t)n_games, 0);
   e->t.budget = nullptr;          // budgets belong to one ply
+  e->t.fast = nullptr;            // and so does the fast-row mask
   e->selected = false;
   e->stepping = true;
   e->multi = e->leaves > 1;
@@ -792,6 +795,31 @@ int fpc_search_set_budget(fpc_engine *e, const int *budget, int n_games) {
   // pageable host memory: the copy has left `budget` when the call returns
   HIPCHK(e, hipMemcpyAsync(e->d_budget, budget, (size_t)n_games * sizeof(int), hipMemcpyHostToDevice, e->stream));
   e->t.budget = e->d_budget;
+  return 0;
+}
+
+int fpc_search_set_fast_rows(fpc_engine *e, const uint8_t *fast, int n_games) {
+  if (!e) return fail(e, FPC_EINVAL, "null engine");
+  if (!e->searching)
+    return fail(e, FPC_ESTATE, "fpc_search_set_fast_rows needs a search in progress: after fpc_search_begin / fpc_search_advance(_refill)");
+  if (e->selected && e->stepping)
+    return fail(e, FPC_ESTATE, "fpc_search_set_fast_rows: a selection has been issued since the last fpc_search_begin / fpc_search_advance");
+  if (e->selected)
+    return fail(e, FPC_ESTATE, "fpc_search_set_fast_rows: the search is finished (fpc_search_results has been read): advance it or begin another");
+  if (n_games != e->G) return fail(e, FPC_EINVAL, "fpc_search_set_fast_rows: n_games %d, the search has %d games", n_games, e->G);
+  if (!fast) {
+    e->t.fast = nullptr;
+    return 0;
+  }
+  for (int g = 0; g < n_games; ++g)
+    if (fast[g] > 1) return fail(e, FPC_EINVAL, "fpc_search_set_fast_rows: fast[%d] = %d is neither 0 nor 1", g, (int)fast[g]);
+  USE_DEV(e);
+  int r;
+  // whole words: the FORCE instances of select_game read the aligned word that holds a game's byte
+  if (!e->d_fast && (r = dalloc(e, &e->d_fast, ((size_t)e->cfg.max_games + 3) & ~(size_t)3))) return r;
+  // pageable host memory: the copy has left `fast` when the call returns
+  HIPCHK(e, hipMemcpyAsync(e->d_fast, fast, (size_t)n_games, hipMemcpyHostToDevice, e->stream));
+  e->t.fast = e->d_fast;
   return 0;
 }
 
@@ -1103,6 +1131,7 @@ static int advance_impl(fpc_engine *e, const int *src_game, const int *flat, con
   e->rows_k = 1;
   e->pending_vl = false;
   e->t.budget = nullptr;          // budgets belong to one ply
+  e->t.fast = nullptr;            // and so does the fast-row mask
   e->selected = false;
   std::vector<int> kept(n_games), errs(n_games);
   HIPCHK(e, hipMemcpyAsync(kept.data(), e->d_rc_meta, (size_t)n_games * sizeof(int), hipMemcpyDeviceToHost, e->stream));
@@ -1433,7 +1462,8 @@ int fpc_replay_read(fpc_engine *e, int ring, fpc_tuple *host_out, int first_slot
   return 0;
 }
 
-int fpc_replay_batch(fpc_engine *e, int ring, const int *slot, int n, float *enc_dev, float *pi_dev, float *z_dev) {
+// fpc_replay_batch (w_dev null) and fpc_replay_batch_w
+static int replay_batch(fpc_engine *e, int ring, const int *slot, int n, float *enc_dev, float *pi_dev, float *z_dev, float *w_dev) {
   if (!e || bad_ring(ring) || n < 0 || !slot || !enc_dev || !pi_dev || !z_dev) return fail(e, FPC_EINVAL, "fpc_replay_batch: bad argument");
   if (((uintptr_t)enc_dev | (uintptr_t)pi_dev) & 15) return fail(e, FPC_EINVAL, "fpc_replay_batch: enc_dev and pi_dev must be 16-byte aligned");
   const fpc_engine::Ring &g = e->ring[ring];
@@ -1450,13 +1480,22 @@ int fpc_replay_batch(fpc_engine *e, int ring, const int *slot, int n, float *enc
     HIPCHK(e, hipEventCreate(&e->rp_ev[1]));
   }
   if (e->timing) HIPCHK(e, hipEventRecord(e->rp_ev[0], e->stream));
-  FPC_LAUNCH(k_replay_decode, n, RD_THREADS, e->stream, e->dc, (const fpc_tuple *)g.d, (const int *)e->d_rp_idx, n, enc_dev, pi_dev, z_dev);
+  FPC_LAUNCH(k_replay_decode, n, RD_THREADS, e->stream, e->dc, (const fpc_tuple *)g.d, (const int *)e->d_rp_idx, n, enc_dev, pi_dev, z_dev, w_dev);
   HIPCHK(e, hipGetLastError());
   if (e->timing) HIPCHK(e, hipEventRecord(e->rp_ev[1], e->stream));
   HIPCHK(e, hipStreamSynchronize(e->stream));
   e->rp_decode_ms = -1.f;
   if (e->timing) HIPCHK(e, hipEventElapsedTime(&e->rp_decode_ms, e->rp_ev[0], e->rp_ev[1]));
   return 0;
+}
+
+int fpc_replay_batch(fpc_engine *e, int ring, const int *slot, int n, float *enc_dev, float *pi_dev, float *z_dev) {
+  return replay_batch(e, ring, slot, n, enc_dev, pi_dev, z_dev, nullptr);
+}
+
+int fpc_replay_batch_w(fpc_engine *e, int ring, const int *slot, int n, float *enc_dev, float *pi_dev, float *z_dev, float *w_dev) {
+  if (!w_dev) return fail(e, FPC_EINVAL, "fpc_replay_batch_w: null w_dev");
+  return replay_batch(e, ring, slot, n, enc_dev, pi_dev, z_dev, w_dev);
 }
 
 int fpc_replay_decode_ms(fpc_engine *e, float *ms_out) {

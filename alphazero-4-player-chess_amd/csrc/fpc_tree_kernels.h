@@ -99,6 +99,11 @@ struct Tree {
   // forced playouts and policy target pruning at the root (fpc_search_set_forced; 0: off): the factor k.  Read by the FORCE
   // instances of the selecting kernels at the root level only, and by root_targets.  Last in the struct: no other field moves.
   double forced;
+  // playout cap randomization (fpc_search_set_fast_rows; null: none): [G] bytes, 1 where the game's search of this ply is a
+  // FAST search -- no forcing in its selection (the FORCE instances only read it), no pruning of its target (k_root_targets,
+  // k_collect_tuples, k_play_ply), FPC_TUPLE_FAST in its record.  Set and cleared where `budget` is.  The allocation is
+  // padded to a multiple of 4 bytes and 4-byte aligned: select_game reads the word that holds a game's byte.  Last in the struct.
+  const uint8_t *fast;
 };
 __host__ __forceinline__ int born_visits(int rules) { return (rules & FPC_RULES_VISITS) ? 0 : 1; }
 
@@ -1292,6 +1297,7 @@ __global__ void __launch_bounds__(64) k_root_targets(Tree t, int G, int maxc, do
   const int c0 = t.child0[nb], nc = c0 < 0 ? 0 : (int)t.nch[nb];
   int *out = target + (size_t)g * maxc;
   for (int k = lane; k < maxc; k += 64) out[k] = k < nc ? t.N[nb + c0 + k] : 0;
+  if (t.fast != nullptr && t.fast[g]) prune = 0;     // a fast search's target is not pruned (fpc_search_set_fast_rows)
   // the same lane owns child k in both loops: its second store follows its first
   if (prune) root_targets(t, nb, c0, nc, Cpuct, [&](int k, int T) { if (k < maxc) out[k] = T; });
 }
@@ -1312,11 +1318,14 @@ __global__ void __launch_bounds__(64) k_collect_tuples(Tree t, int G, const int 
     rec->flat[k] = in ? t.mv[nb + c0 + k] : (uint16_t)0;
     rec->visits[k] = in ? (uint16_t)t.N[nb + c0 + k] : (uint16_t)0;
   }
+  // a fast search (fpc_search_set_fast_rows): the stored counts stay, and the record says so
+  const int fast = t.fast != nullptr && t.fast[g] ? 1 : 0;
+  if (fast) prune = 0;
   // the same lane owns child k in both loops: its second store follows its first
   if (prune) root_targets(t, nb, c0, nc, Cpuct, [&](int k, int T) { if (k < FPC_TUPLE_MAXC) rec->visits[k] = (uint16_t)T; });
   if (lane < 44) rec->pad1[lane] = 0;
   if (lane == 0) {
-    rec->turn = root->turn; rec->pad0 = 0;
+    rec->turn = root->turn; rec->flags = (uint8_t)(fast ? FPC_TUPLE_FAST : 0);
     rec->n = (uint16_t)(nc < FPC_TUPLE_MAXC ? nc : FPC_TUPLE_MAXC);
     rec->z = 0.f; rec->game = game_id ? game_id[g] : g; rec->ply = ply;
   }
@@ -1368,6 +1377,7 @@ __global__ void __launch_bounds__(64) k_play_ply(DevCfg c, Tree t, int G, const 
     if (lane == 0) { flat[g] = -1; result[g] = -1; err[g] = 0; }
     return;
   }
+  if (t.fast != nullptr && t.fast[g]) prune = 0;     // a fast search draws from the stored counts (fpc_search_set_fast_rows)
   if (prune) {                                       // wave-uniform; T_k <= N_k, the clamp as below
     root_targets(t, nb, c0, nc, Cpuct, [&](int k, int n) { wt[k] = argmax ? (double)n : powtab[n < 0 ? 0 : n < powtab_n ? n : powtab_n - 1]; });
   } else
@@ -1460,7 +1470,8 @@ __global__ void __launch_bounds__(64) k_replay_store(const fpc_tuple *src, const
 //                    one IEEE f32 division, so the row has the bits of tuples.dense_pi (S <= 256 * 65535 < 2^24: torch's
 //                    f32 sum is exact in any order).  n == 0 gives an all-zero row, and so does S == 0 (a root none of whose
 //                    children has a visit, FPC_RULES_VISITS), as in dense_pi.  A flat >= A (never made by a search) is dropped;
-//   z[i]             rec.z.
+//   z[i]             rec.z;
+//   w[i]             (w not null: fpc_replay_batch_w) 0.0f for a record with FPC_TUPLE_FAST, else 1.0f.
 // Thread k owns child k (RD_THREADS == FPC_TUPLE_MAXC).  Both rows leave as 16-byte stores, lane after lane (enc and pi
 // rows start on 16-byte boundaries: 24*RR and A = 8(R+1)RR are multiples of 4 floats).  The at most 256 nonzeros of pi
 // are 4-byte stores into the row this workgroup has just zeroed, ordered behind the zero fill by the barrier
@@ -1468,7 +1479,7 @@ __global__ void __launch_bounds__(64) k_replay_store(const fpc_tuple *src, const
 constexpr int RD_THREADS = 256;
 static_assert(RD_THREADS == FPC_TUPLE_MAXC && RD_THREADS >= FPC_MAX_SQ, "k_replay_decode: one thread per child, one per square");
 __global__ void __launch_bounds__(RD_THREADS) k_replay_decode(DevCfg c, const fpc_tuple *ring, const int *slot, int n,
-                                                              float *enc, float *pi, float *z) {
+                                                              float *enc, float *pi, float *z, float *w) {
   __shared__ int8_t s_plane[FPC_MAX_SQ];           // input plane of the piece on each square of the rotated board, -1 empty
   __shared__ int s_sum[RD_THREADS / 64];
   const int i = blockIdx.x;
@@ -1489,7 +1500,10 @@ __global__ void __launch_bounds__(RD_THREADS) k_replay_decode(DevCfg c, const fp
   if ((tid & 63) == 0) s_sum[tid >> 6] = s;
   __syncthreads();
   const int S = s_sum[0] + s_sum[1] + s_sum[2] + s_sum[3];
-  if (tid == 0) z[i] = rec->z;
+  if (tid == 0) {
+    z[i] = rec->z;
+    if (w != nullptr) w[i] = (rec->flags & FPC_TUPLE_FAST) ? 0.0f : 1.0f;     // fpc_replay_batch_w: the policy-loss weight
+  }
   float4 *e4 = reinterpret_cast<float4 *>(enc + (size_t)i * 24 * RR);
   // (plane, square) of a piece's first float, carried from piece to piece: one division per thread, none per piece
   const int dplane = (4 * RD_THREADS) / RR, dpos = 4 * RD_THREADS - dplane * RR;
@@ -1647,6 +1661,22 @@ __device__ inline void select_game(WaveLds &s, const DevCfg &c, const Tree &t, i
   int Nst = Nn;
   int rootS = 0;                             // the solver: the root's status, with the batch above
   if constexpr (SOLVE) rootS = t.S[nb];
+  // Playout cap (fpc_search_set_fast_rows): a fast game's root level is not forced.  The game's byte goes out with the batch
+  // above, as the aligned word that holds it (the array is padded to whole words and zeroed when it is allocated): gfx950
+  // has no scalar byte load, and the word is a scalar load issued beside the one of t.alive[g] and waited for with it.
+  // With no mask the game's liveness word stands in and is ignored.  Wave-uniform; an instance without FORCE issues no load.
+  bool force_here = FORCE;
+  if constexpr (FORCE) {
+    uint32_t word;
+#ifdef FPC_EMUL
+    const void *fw = t.fast != nullptr ? (const void *)(t.fast + (g & ~3)) : (const void *)(t.alive + g);
+    __builtin_memcpy(&word, fw, sizeof word);      // host build: no access through a pointer of another type
+#else
+    const uint32_t *fw = t.fast != nullptr ? reinterpret_cast<const uint32_t *>(t.fast) + (g >> 2) : reinterpret_cast<const uint32_t *>(t.alive + g);
+    word = *fw;
+#endif
+    force_here = t.fast == nullptr || ((word >> ((g & 3) * 8)) & 0xffu) == 0;
+  }
   if constexpr (MULTI) { m->leaf_vl = m->lp.VL[nb]; Nn += m->leaf_vl; }
   if (!is_alive || room <= 0) {             // root already removed from the search (Q5), or the game is at its budget: a dead row
     if (lane == 0) { leaf_node[FPC_ROW] = -1; leaf_slot[FPC_ROW] = -1; }
@@ -1711,7 +1741,7 @@ __device__ inline void select_game(WaveLds &s, const DevCfg &c, const Tree &t, i
           const double q = Nc > 0 ? -(Wc / (double)Nc) : q0;
           u = q + Cpuct * Pc * sqrtNp / (double)(1 + Nc);
           if constexpr (FORCE) {                     // in effect only under FPC_RULES_PUCT: this branch
-            if (n == 0 && Nc > 0 && (double)Nc < sqrt(t.forced * Pc * (double)Nn)) u = __builtin_inf();
+            if (n == 0 && force_here && Nc > 0 && (double)Nc < sqrt(t.forced * Pc * (double)Nn)) u = __builtin_inf();
           }
         } else {
           const double q = Nc > 0 ? Wc / (double)Nc : 0.0;

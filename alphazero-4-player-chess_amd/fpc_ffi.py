@@ -49,11 +49,12 @@ class Stats(C.Structure):
 
 
 MAX_TUPLE_C = 256
+TUPLE_FAST = 1          # fpc_tuple::flags bit: the record comes from a fast search (fpc_search_set_fast_rows)
 
 
 class Tuple(C.Structure):
     """fpc_tuple: one (state, pi, z) training record, 1280 bytes (include/fpc_engine.h)."""
-    _fields_ = [("sq", C.c_uint8 * MAX_SQ), ("turn", C.c_uint8), ("pad0", C.c_uint8), ("n", C.c_uint16), ("z", C.c_float),
+    _fields_ = [("sq", C.c_uint8 * MAX_SQ), ("turn", C.c_uint8), ("flags", C.c_uint8), ("n", C.c_uint16), ("z", C.c_float),
                 ("game", C.c_int32), ("ply", C.c_int32), ("flat", C.c_uint16 * MAX_TUPLE_C), ("visits", C.c_uint16 * MAX_TUPLE_C),
                 ("pad1", C.c_uint8 * 44)]
 
@@ -144,6 +145,7 @@ _SIGS = {
     "fpc_search_advance": (C.c_int, [C.c_void_p, P(C.c_int), P(C.c_int), C.c_int, P(Board), P(C.c_int)]),
     "fpc_search_advance_refill": (C.c_int, [C.c_void_p, P(C.c_int), P(C.c_int), P(Board), C.c_int, P(Board), P(C.c_int)]),
     "fpc_search_set_budget": (C.c_int, [C.c_void_p, P(C.c_int), C.c_int]),
+    "fpc_search_set_fast_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
     "fpc_search_play": (C.c_int, [C.c_void_p, C.c_double, P(C.c_double), P(C.c_int), P(C.c_int), P(Board)]),
     "fpc_search_play_ms": (C.c_int, [C.c_void_p, P(C.c_float)]),
     "fpc_search_grandchildren": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, P(C.c_int), C.c_void_p, C.c_void_p]),
@@ -192,6 +194,7 @@ _SIGS = {
     "fpc_replay_size": (C.c_int, [C.c_void_p, C.c_int]),
     "fpc_replay_read": (C.c_int, [C.c_void_p, C.c_int, P(Tuple), C.c_int, C.c_int]),
     "fpc_replay_batch": (C.c_int, [C.c_void_p, C.c_int, P(C.c_int), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fpc_replay_batch_w": (C.c_int, [C.c_void_p, C.c_int, P(C.c_int), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "fpc_replay_decode_ms": (C.c_int, [C.c_void_p, P(C.c_float)]),
 }
 EXPORTS = sorted(_SIGS)
@@ -482,6 +485,19 @@ class Engine:
         b = np.ascontiguousarray(budget, np.int32)
         assert b.ndim == 1
         self._chk(self.L.fpc_search_set_budget(self.h, C.cast(b.ctypes.data, P(C.c_int)), int(b.shape[0])))
+
+    def search_set_fast_rows(self, fast):
+        """playout cap randomization (include/fpc_engine.h fpc_search_set_fast_rows): fast[g] true marks game g's search of
+        this ply as a fast search -- no forced playouts in its selection, no pruning of its target, TUPLE_FAST in its
+        record.  Noise is the caller's: give a fast row an all-zero gamma row.  Set after search_begin /
+        search_advance(_refill) and before the search's first selection; None clears the mask, and so does every later
+        begin / advance."""
+        if fast is None:
+            self._chk(self.L.fpc_search_set_fast_rows(self.h, None, self.G))
+            return
+        m = np.ascontiguousarray(fast, np.uint8)
+        assert m.ndim == 1
+        self._chk(self.L.fpc_search_set_fast_rows(self.h, m.ctypes.data, int(m.shape[0])))
 
     def search_finish(self):
         """fpc_search_results with every array NULL: waits for the search, reads the games' error words (raises on one)
@@ -800,14 +816,16 @@ class Engine:
         self._chk(self.L.fpc_replay_read(self.h, int(ring), arr, int(first), int(n)))
         return arr, n
 
-    def replay_batch(self, ring, slots, enc, pi, z):
+    def replay_batch(self, ring, slots, enc, pi, z, w=None):
         """decode the records in `slots` (any order, repeats allowed) into enc [n,24,R,R], pi [n,A], z [n] (f32, device
         memory; on the emulator, host memory): contiguous torch tensors / numpy arrays, or raw pointers.  One launch;
-        the engine's stream is synchronised before this returns."""
+        the engine's stream is synchronised before this returns.  w (optional, [n] f32): the records' policy-loss weights,
+        0.0 for a record with TUPLE_FAST and 1.0 otherwise (fpc_replay_batch_w)."""
         sl = np.ascontiguousarray(slots, np.int32)
         n = int(sl.shape[0])
         ptrs = []
-        for t, shape in ((enc, (n, 24, self.R, self.R)), (pi, (n, self.A)), (z, (n,))):
+        outs = [(enc, (n, 24, self.R, self.R)), (pi, (n, self.A)), (z, (n,))] + ([] if w is None else [(w, (n,))])
+        for t, shape in outs:
             if isinstance(t, int):
                 ptrs.append(t)
                 continue
@@ -820,7 +838,8 @@ class Engine:
         if (ptrs[0] | ptrs[1]) & 15:
             raise ValueError("replay_batch: enc and pi must start on a 16-byte boundary (the kernel writes 16-byte pieces); "
                              "a sliced view with an odd storage offset does not -- pass a tensor of its own")
-        self._chk(self.L.fpc_replay_batch(self.h, int(ring), C.cast(sl.ctypes.data, P(C.c_int)), n, *ptrs))
+        fn = self.L.fpc_replay_batch if w is None else self.L.fpc_replay_batch_w
+        self._chk(fn(self.h, int(ring), C.cast(sl.ctypes.data, P(C.c_int)), n, *ptrs))
 
     def replay_decode_ms(self):
         """HIP-event time of k_replay_decode in the last replay_batch (set_timing(True) first)"""

@@ -32,6 +32,11 @@ None (default) | float, usually 2.0 -- with args["root_noise"] under args["rules
 guaranteed sqrt(k * P * N) simulations, and the policy target (fpc_collect_tuples, fpc_search_play, fpc_search_targets /
 selfplay.play(targets=True)) leaves out the visits that only the forcing put there.
 
+Playout cap randomization (opt-in; include/fpc_engine.h fpc_search_set_fast_rows): args["playout_cap"] = None (default) |
+{"full_prob": p, "fast_searches": n}, 0 < p <= 1, 1 <= n <= num_searches -- search / continue_search take fast=[bool per
+game]: a fast game is searched with n simulations, an all-zero noise row and no forcing, and its target is not pruned;
+selfplay.play(playout_cap=...) draws which plies are fast, and the trainer leaves their policy targets out.
+
 Live-row numbering (opt-in; include/fpc_engine.h fpc_search_set_live_rows): args["live_rows"] = True makes every step work
 on its live leaves only -- the same trees; the fused search's policy Linear computes ceil(live / 256) row tiles, and an
 external evaluator sees [n_live,24,R,R] (the live leaves in ascending row order) and returns n_live rows.
@@ -67,7 +72,23 @@ def _on_engine_device(m, eng):
 SIM_BUDGET_MODES = (None, "per_game", "visit_target")
 
 
-def budgets_for(kept, num_searches, max_sims, mode, born=1):
+def parse_playout_cap(cap, num_searches):
+    """args["playout_cap"] checked: None, or (full_prob, fast_searches) of {"full_prob": p, "fast_searches": n} with
+    0 < p <= 1 and 1 <= n <= num_searches (further keys, such as alphazero's "record_fast", are the caller's)"""
+    if cap is None:
+        return None
+    try:
+        p, n = cap["full_prob"], cap["fast_searches"]
+    except (TypeError, KeyError, IndexError):
+        raise ValueError("playout_cap must be None or {\"full_prob\": p, \"fast_searches\": n}, not %r" % (cap,))
+    if isinstance(p, bool) or not isinstance(p, (int, float)) or not 0 < p <= 1:
+        raise ValueError("playout_cap: full_prob must lie in (0, 1], not %r" % (p,))
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 1 <= n <= int(num_searches):
+        raise ValueError("playout_cap: fast_searches must be an int in 1..num_searches = %d, not %r" % (int(num_searches), n))
+    return float(p), int(n)
+
+
+def budgets_for(kept, num_searches, max_sims, mode, born=1, fast=None, fast_searches=None):
     """Per-game simulation budgets of one ply (fpc_search_set_budget) from the roots' kept visit counts (1 for a fresh
     root, so kept - 1 simulations have gone through a root already); None for mode None.  born: the visit count a node is
     born with -- 1, or 0 under fpc_ffi.RULES_VISITS, where `kept` itself is the simulations through the root and stands
@@ -75,15 +96,24 @@ def budgets_for(kept, num_searches, max_sims, mode, born=1):
     "per_game":     min(num_searches, max_sims - (kept - 1)): every game gets num_searches unless ITS OWN kept visits
                     leave less room in the handle -- a fresh row gets its full count beside any kept root.
     "visit_target": max(0, num_searches - (kept - 1)): every root is searched until num_searches simulations have gone
-                    through it (kept + new <= num_searches, so a handle of num_searches simulations is enough)."""
+                    through it (kept + new <= num_searches, so a handle of num_searches simulations is enough).
+    fast (optional, one bool per game; playout cap randomization): a fast game's budget is the same expression with
+    fast_searches in place of num_searches.  Without it the result is what it was."""
     if mode not in SIM_BUDGET_MODES:
         raise ValueError("sim_budget must be one of %r, not %r" % (SIM_BUDGET_MODES, mode))
     if mode is None:
         return None
-    S, M = int(num_searches), int(max_sims)
+    M = int(max_sims)
+    S = [int(num_searches)] * len(kept)
+    if fast is not None:
+        if len(fast) != len(kept):
+            raise ValueError("budgets_for: %d fast flags for %d games" % (len(fast), len(kept)))
+        if fast_searches is None:
+            raise ValueError("budgets_for: fast rows need fast_searches")
+        S = [int(fast_searches) if f else s for f, s in zip(fast, S)]
     if mode == "per_game":
-        return [max(0, min(S, M - (int(k) - born))) for k in kept]
-    return [max(0, S - (int(k) - born)) for k in kept]
+        return [max(0, min(s, M - (int(k) - born))) for k, s in zip(kept, S)]
+    return [max(0, s - (int(k) - born)) for k, s in zip(kept, S)]
 
 
 class MCTS:
@@ -139,6 +169,26 @@ class MCTS:
             raise ValueError("sim_budget must be one of %r, not %r" % (SIM_BUDGET_MODES, self.sim_budget))
         # args["live_rows"] = True (opt-in): only the live leaves of a step are evaluated (fpc_search_set_live_rows)
         self.live_rows = bool(args.get("live_rows", False)) if hasattr(args, "get") else False
+        # args["playout_cap"] = None (default) | {"full_prob": p, "fast_searches": n} (opt-in): playout cap randomization
+        # (fpc_search_set_fast_rows) -- search / continue_search accept fast=[...]; who is fast is selfplay.play's draw
+        cap = args.get("playout_cap", None) if hasattr(args, "get") else None
+        self.playout_cap = None if cap is None else parse_playout_cap(cap, args["num_searches"])
+
+    def _fast_rows(self, fast, G):
+        """the fast= argument of search / continue_search as a list of G bools (None: none given)"""
+        if fast is None:
+            return None
+        if self.playout_cap is None:
+            raise ValueError("fast= needs args[\"playout_cap\"]")
+        fast = [bool(f) for f in fast]
+        if len(fast) != G:
+            raise ValueError("%d fast flags for %d games" % (len(fast), G))
+        return fast
+
+    def _fast_budgets(self, kept, fast, max_sims):
+        """the budgets of a ply with fast rows: budgets_for with fast_searches for them; no sim_budget counts as "per_game\""""
+        return budgets_for(kept, int(self.args["num_searches"]), max_sims, self.sim_budget or "per_game", self.born, fast=fast,
+                           fast_searches=self.playout_cap[1])
 
     def solver_in_effect(self):
         return self.solver and (int(self.rules) & 17) == 17       # RULES_PUCT | RULES_TERMINAL
@@ -179,10 +229,13 @@ class MCTS:
         return policy * (1.0 - eps) + noise * eps
 
     @torch.no_grad()
-    def search(self, games, budgets=None):
+    def search(self, games, budgets=None, fast=None):
         """budgets (optional): per-game simulation counts of this search (fpc_search_set_budget), each at most
-        num_searches -- game g completes budgets[g] simulations while the batch runs max(budgets) steps' worth."""
+        num_searches -- game g completes budgets[g] simulations while the batch runs max(budgets) steps' worth.
+        fast (optional, one bool per game; needs args["playout_cap"]): the fast games get an all-zero noise row, the
+        fast-row mask (fpc_search_set_fast_rows) and, unless `budgets` is given, fast_searches simulations."""
         G = len(games)
+        fast = self._fast_rows(fast, G)
         sims = int(self.args["num_searches"])
         eng = az.engine(self.engine_rows(G), sims, self.nn_dtype if self._native else None)
         pods = [g._b for g in games]
@@ -192,10 +245,16 @@ class MCTS:
         if self.root_noise:
             import fpc_ffi
             gamma = self._noise_rng.standard_gamma(float(self.args["dirichlet_alpha"]), size=(G, fpc_ffi.MAX_MOVES)).astype(np.float32)
+            if fast is not None:
+                gamma[np.asarray(fast, bool)] = 0.0        # a row whose sum is not positive keeps its priors un-noised
             eng.set_root_noise(gamma, float(self.args["dirichlet_epsilon"]))
         else:
             eng.set_root_noise(None, 0.0)
         eng.search_begin(pods, float(self.args["C"]))
+        if fast is not None:
+            eng.search_set_fast_rows(fast)
+            if budgets is None:
+                budgets = self._fast_budgets([self.born] * G, fast, eng.max_sims)
         eng.set_live_rows(self.live_rows)                  # as set_leaves; here, where no selection can be pending
         eng.set_solver(self.solver)                        # the same; begin has cleared the statuses
         eng.set_forced(self.forced)
@@ -223,7 +282,7 @@ class MCTS:
         return roots
 
     @torch.no_grad()
-    def continue_search(self, pods, keep_idx, flats, budgets=None):
+    def continue_search(self, pods, keep_idx, flats, budgets=None, fast=None):
         """Opt-in subtree reuse (not reference semantics; include/fpc_engine.h fpc_search_advance), for callers that know
         the moves played -- selfplay.play(continue_fn=...); the drop-in search(games) carries no move history and always
         starts fresh trees.  Re-roots the search this object ran last: new game i continues game keep_idx[i] of it from
@@ -234,8 +293,11 @@ class MCTS:
         batch-wide simulation count.
         With args["sim_budget"] set, or an explicit `budgets` list (which overrides the mode), every game gets its own
         simulation count instead (budgets_for / fpc_search_set_budget) and the batch runs max(budget) steps' worth.
+        fast (optional, one bool per game; needs args["playout_cap"]): as in search(); the noise row of a fast game is
+        zeroed before the advance blends it.
         Returns the fpc_ffi.Engine.search_results dict."""
         G = len(flats)
+        fast = self._fast_rows(fast, G)
         eng = az.engine()
         eng.set_rule_bits(int(self.rules))                 # all six bits; set_rules keeps its range 0..31
         eng.set_leaves(self.leaves, self.virtual_loss)
@@ -243,6 +305,8 @@ class MCTS:
         if self.root_noise:
             import fpc_ffi
             gamma = self._noise_rng.standard_gamma(float(self.args["dirichlet_alpha"]), size=(G, fpc_ffi.MAX_MOVES)).astype(np.float32)
+            if fast is not None:
+                gamma[np.asarray(fast, bool)] = 0.0        # a row whose sum is not positive keeps its priors un-noised
             eng.set_root_noise(gamma, float(self.args["dirichlet_epsilon"]))
         else:
             eng.set_root_noise(None, 0.0)
@@ -251,6 +315,10 @@ class MCTS:
             kept = eng.search_advance_refill(flats, keep_idx, fresh=pods, roots=pods)
         else:
             kept = eng.search_advance(flats, keep_idx, roots=pods)
+        if fast is not None:
+            eng.search_set_fast_rows(fast)
+            if budgets is None:
+                budgets = self._fast_budgets(kept, fast, eng.max_sims)
         eng.set_live_rows(self.live_rows)
         eng.set_solver(self.solver)
         eng.set_forced(self.forced)

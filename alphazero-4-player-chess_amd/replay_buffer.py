@@ -29,6 +29,8 @@ class DeviceReplayBuffer:
     `engine`, filled by Engine.replay_push / replay_load.  sample() draws the positions ReplayBuffer.sample draws from a
     buffer of the same length (random.sample picks by position from the population size alone) and decodes them in one
     kernel launch: (x [n,24,R,R], pi [n,A], z [n,1]) f32 on `device` (None: host memory, the emulator backend).
+    decode / sample with weights=True return a fourth tensor w [n,1]: 0.0 for a record of a fast search (playout cap
+    randomization, fpc_ffi.TUPLE_FAST), 1.0 otherwise -- the record's weight in the policy loss.
     An engine has one ring of each number: making a second buffer on the same engine and ring empties the ring under the
     first one, whose next use then raises."""
 
@@ -48,17 +50,18 @@ class DeviceReplayBuffer:
         self._mine()
         return self.eng.replay_size(self.ring)
 
-    def decode(self, slots):
+    def decode(self, slots, weights=False):
         import torch
         self._mine()
         n, e = len(slots), self.eng
         kw = {"dtype": torch.float32, "device": self.device if self.device is not None else "cpu"}
         x, pi, z = torch.empty((n, 24, e.R, e.R), **kw), torch.empty((n, e.A), **kw), torch.empty((n, 1), **kw)
+        w = torch.empty((n, 1), **kw) if weights else None
         if n:
             if self.device is not None:
                 torch.cuda.current_stream(self.device).synchronize()    # the allocator may hand out blocks queued work still reads
-            e.replay_batch(self.ring, slots, x, pi, z)
-        return x, pi, z
+            e.replay_batch(self.ring, slots, x, pi, z, w=w)
+        return (x, pi, z, w) if weights else (x, pi, z)
 
-    def sample(self, batch_size):
-        return self.decode(self._rng.sample(range(len(self)), batch_size))
+    def sample(self, batch_size, weights=False):
+        return self.decode(self._rng.sample(range(len(self)), batch_size), weights=weights)

@@ -90,6 +90,7 @@ class Episode:
         self.gid = gid
         self.start = start      # the loop step of the game's first search (0 unless the game came in through `refill`)
         self.entries = []       # (board POD snapshot, flats, visits)
+        self.fast = []          # per entry: the ply's search was a fast one (play(playout_cap=...)); all False without the cap
         self.moves = []
         self.z = []             # per entry
         self.result = 0
@@ -97,7 +98,7 @@ class Episode:
 
 
 def play(search_fn, eng, start_boards, args, uniforms, continue_fn=None, on_searched=None, device_play=False, refill=None,
-         z_from_result=False, solver=False, targets=False):
+         z_from_result=False, solver=False, targets=False, playout_cap=None, cap_uniforms=None):
     """search_fn(list_of_PODs) -> search_results dict (fpc_ffi.Engine.search_results layout) and
     leaves the PODs with the piece-list order the search produced.  uniforms[ply][gid] in [0,1): the draw of game gid at
     its OWN ply.
@@ -128,7 +129,22 @@ def play(search_fn, eng, start_boards, args, uniforms, continue_fn=None, on_sear
     targets (opt-in, default False; the engine's forced playouts must be in effect -- fpc_search_set_forced under RULES_PUCT
     | RULES_VISITS): Episode.entries hold the pruned visit counts of eng.search_targets() instead of the raw visits, and the
     host loop draws its move from them.  The device path's draw needs no flag: fpc_search_play draws from the same counts.
+    playout_cap (opt-in, default None: the calls above, argument for argument) = {"full_prob": p, "fast_searches": n}, with
+    cap_uniforms[ply][gid] in [0,1): playout cap randomization.  Game gid's search at its OWN ply is a fast search iff
+    cap_uniforms[ply][gid] >= p; the loop calls search_fn(states, fast=[...]) / continue_fn(keep_idx, picks, states,
+    fast=[...]) with one bool per game of the batch (mcts.MCTS.search / continue_search give those games n simulations, no
+    noise and no forcing) and records the flag in Episode.fast, parallel to Episode.entries.  Under targets=True a fast
+    game's entry holds its raw visits, which is what eng.search_targets() reports for it.
     Returns the list of finished Episodes (all games, in game-id order)."""
+    if playout_cap is not None:
+        full_prob = float(playout_cap["full_prob"])
+        if not 0 < full_prob <= 1:
+            raise ValueError("playout_cap: full_prob must lie in (0, 1], not %r" % (playout_cap["full_prob"],))
+        if cap_uniforms is None:
+            raise ValueError("playout_cap needs cap_uniforms")
+        n_all = len(start_boards) + (len(refill) if refill else 0)
+        if len(cap_uniforms) < int(args["max_game_length"]) or any(len(row) < n_all for row in cap_uniforms):
+            raise ValueError("cap_uniforms must be [max_game_length = %d][games = %d]" % (int(args["max_game_length"]), n_all))
     states = [fpc_ffi.clone_board(b) for b in start_boards]
     ids = list(range(len(states)))
     eps = {g: Episode(g) for g in ids}
@@ -136,10 +152,15 @@ def play(search_fn, eng, start_boards, args, uniforms, continue_fn=None, on_sear
     T, L, hw = float(args["temperature"]), int(args["max_game_length"]), float(args["heuristic_weight"])
     step = 0
     while states and L > 0:
-        res = search_fn(states) if continue_fn is None or step == 0 else continue_fn(keep_pos, keep_picks, states)
+        plies = [eps[g].length for g in ids]                     # each game's own ply
+        if playout_cap is None:
+            fast = [False] * len(ids)
+            res = search_fn(states) if continue_fn is None or step == 0 else continue_fn(keep_pos, keep_picks, states)
+        else:
+            fast = [bool(cap_uniforms[p][g] >= full_prob) for p, g in zip(plies, ids)]
+            res = search_fn(states, fast=fast) if continue_fn is None or step == 0 else continue_fn(keep_pos, keep_picks, states, fast=fast)
         if on_searched is not None:
             on_searched(list(ids), step)
-        plies = [eps[g].length for g in ids]                     # each game's own ply
         picks = []
         proofs = eng.search_proofs() if solver and not device_play else None
         counts = eng.search_targets(res["visits"].shape[1]) if targets else res["visits"]
@@ -147,6 +168,7 @@ def play(search_fn, eng, start_boards, args, uniforms, continue_fn=None, on_sear
             n = int(res["n_children"][i])
             flats, visits = res["flat"][i, :n].copy(), counts[i, :n].copy()
             eps[ids[i]].entries.append((fpc_ffi.clone_board(states[i]), flats, visits))
+            eps[ids[i]].fast.append(fast[i])
             if not device_play:
                 forced = None if proofs is None else proven_pick(proofs[0][i], proofs[1][i, :n])
                 picks.append(int(flats[forced]) if forced is not None else sample_action(flats, visits, T, uniforms[plies[i]][ids[i]]))

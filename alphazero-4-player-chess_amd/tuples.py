@@ -6,6 +6,9 @@ rank all-gathers its compact records once per episode over RCCL (backend "nccl" 
 
     record = mailbox R*R bytes | turn u8 | n u16 | z f32 | n x (flat u16, visits u16)
 
+Bit 7 of the turn byte marks a record of a fast search (playout cap randomization, fpc_ffi.TUPLE_FAST); the turn is its
+low two bits.
+
 Dense reference-shaped tensors (encoded state [24,R,R] via the engine, pi [A] = visits/sum) are
 rebuilt on receipt (`dense_pi`).  Variable length => all-gather of byte counts, then one padded
 all-gather of the payload (latency-bound: a single fused collective per episode)."""
@@ -24,9 +27,9 @@ def shard_games(n_games, rank, world):
     return list(range(rank, n_games, world))
 
 
-def pack_record(R, mailbox, turn, z, flats, visits):
+def pack_record(R, mailbox, turn, z, flats, visits, fast=False):
     n = len(flats)
-    head = bytes(mailbox[:R * R]) + struct.pack("<BHf", turn, n, float(z))
+    head = bytes(mailbox[:R * R]) + struct.pack("<BHf", turn | (0x80 if fast else 0), n, float(z))
     body = np.stack([np.asarray(flats, np.uint16), np.asarray(visits, np.uint16)], axis=1).tobytes() if n else b""
     return head + body
 
@@ -40,7 +43,8 @@ def unpack_records(R, buf):
         off += RR + 7
         fv = np.frombuffer(buf, np.uint16, 2 * n, off).reshape(n, 2)
         off += 4 * n
-        out.append({"mailbox": mailbox, "turn": turn, "z": z, "flat": fv[:, 0].astype(np.int64), "visits": fv[:, 1].astype(np.int64)})
+        out.append({"mailbox": mailbox, "turn": turn & 0x7f, "z": z, "flat": fv[:, 0].astype(np.int64), "visits": fv[:, 1].astype(np.int64),
+                    "fast": bool(turn & 0x80)})
     return out
 
 
@@ -71,14 +75,15 @@ def all_gather_bytes(payload, device="cpu", group=None):
 
 # ---- native tuples (fpc_tuple PODs built on the device by fpc_collect_tuples) -------------------
 def records_of(arr, n, R):
-    """ctypes fpc_tuple array -> list of record dicts (same keys as unpack_records + game, ply)"""
+    """ctypes fpc_tuple array -> list of record dicts (same keys as unpack_records + game, ply); "fast": the record has
+    fpc_ffi.TUPLE_FAST"""
     out = []
     for i in range(n):
         t = arr[i]
         k = int(t.n)
         out.append({"mailbox": np.frombuffer(bytes(t.sq), np.uint8, R * R).copy(), "turn": int(t.turn), "z": float(t.z),
                     "flat": np.asarray(t.flat[:k], np.int64), "visits": np.asarray(t.visits[:k], np.int64),
-                    "game": int(t.game), "ply": int(t.ply)})
+                    "game": int(t.game), "ply": int(t.ply), "fast": bool(int(t.flags) & fpc_ffi.TUPLE_FAST)})
     return out
 
 
@@ -171,9 +176,15 @@ def init_comm(eng, device=None, group=None):
     return True, ""
 
 
-def dense_batch(eng, recs):
+def weights_of(recs):
+    """[n,1] f32 policy-loss weights: 0.0 for a record of a fast search, 1.0 otherwise (what fpc_replay_batch_w writes)"""
+    return torch.tensor([0.0 if r.get("fast", False) else 1.0 for r in recs], dtype=torch.float32).view(-1, 1)
+
+
+def dense_batch(eng, recs, weights=False):
     """(encoded state [n,24,R,R] f32, pi [n,A] f32, z [n,1] f32) as the reference's trainer stacks them
-    (alphazero.py:186-197): GetEncodedState per tuple (own rotation), pi = N / sum N"""
+    (alphazero.py:186-197): GetEncodedState per tuple (own rotation), pi = N / sum N.  weights=True: a fourth tensor,
+    weights_of(recs)."""
     boards = []
     for r in recs:
         b = fpc_ffi.Board()
@@ -186,7 +197,7 @@ def dense_batch(eng, recs):
     enc = np.concatenate([eng.encode([b]) for b in boards]) if boards else np.zeros((0, 24, eng.R, eng.R), np.float32)
     pi = torch.stack([dense_pi(r, eng.A) for r in recs]) if recs else torch.zeros(0, eng.A)
     z = torch.tensor([r["z"] for r in recs], dtype=torch.float32).view(-1, 1)
-    return torch.from_numpy(enc), pi, z
+    return (torch.from_numpy(enc), pi, z, weights_of(recs)) if weights else (torch.from_numpy(enc), pi, z)
 
 
 def tuples_of(recs):
@@ -197,6 +208,7 @@ def tuples_of(recs):
         C.memmove(t.sq, mb.ctypes.data, mb.shape[0])
         t.turn, t.n, t.z = int(r["turn"]), len(r["flat"]), float(r["z"])
         t.game, t.ply = int(r.get("game", 0)), int(r.get("ply", 0))
+        t.flags = fpc_ffi.TUPLE_FAST if r.get("fast", False) else 0
         fv = np.zeros((2, fpc_ffi.MAX_TUPLE_C), np.uint16)
         fv[0, :t.n], fv[1, :t.n] = r["flat"], r["visits"]
         C.memmove(t.flat, fv[0].ctypes.data, 2 * fpc_ffi.MAX_TUPLE_C)
@@ -204,17 +216,19 @@ def tuples_of(recs):
     return arr
 
 
-def dense_batch_device(eng, recs, device="cuda"):
+def dense_batch_device(eng, recs, device="cuda", weights=False):
     """dense_batch's three tensors, bit for bit, left on `device` (None: host memory, the emulator backend) by one upload
-    of the records and one decode launch on the engine's scratch ring (fpc_replay_load + fpc_replay_batch)"""
+    of the records and one decode launch on the engine's scratch ring (fpc_replay_load + fpc_replay_batch).  weights=True:
+    a fourth tensor [n,1], the weight column of fpc_replay_batch_w."""
     n = len(recs)
     kw = {"dtype": torch.float32, "device": device if device is not None else "cpu"}
     enc, pi, z = torch.empty((n, 24, eng.R, eng.R), **kw), torch.empty((n, eng.A), **kw), torch.empty((n, 1), **kw)
+    w = torch.empty((n, 1), **kw) if weights else None
     if n:
         # the scratch ring only grows: its current capacity again empties it without touching the allocation
         eng.replay_reserve(fpc_ffi.REPLAY_SCRATCH, max(n, eng.replay_cap[fpc_ffi.REPLAY_SCRATCH]))
         eng.replay_load(fpc_ffi.REPLAY_SCRATCH, tuples_of(recs), n)
         if device is not None:
             torch.cuda.current_stream(device).synchronize()
-        eng.replay_batch(fpc_ffi.REPLAY_SCRATCH, np.arange(n), enc, pi, z)
-    return enc, pi, z
+        eng.replay_batch(fpc_ffi.REPLAY_SCRATCH, np.arange(n), enc, pi, z, w=w)
+    return (enc, pi, z, w) if weights else (enc, pi, z)

@@ -436,6 +436,32 @@ int fpc_search_set_forced(fpc_engine *e, double factor);
  * search. */
 int fpc_search_targets(fpc_engine *e, int max_children, int *child_target /* host [G][max_children] */);
 
+/* ---- playout cap randomization: per-game fast searches (opt-in; additions only, fpc_abi_version() unchanged; held against
+ * tests/playout_cap_model.py) ---------------------------------------------------------------------------------------------
+ * KataGo pairs forced playouts and target pruning with playout cap randomization: each ply, each game draws either a FULL
+ * search (N simulations, root noise, forcing; its policy target is trained) or a FAST search (n << N simulations, no noise,
+ * no forcing; no policy target is taken from it).  Games finish sooner for the same network evaluations, every position
+ * still gets a value target, and the policy targets that remain all come from full-strength searches.  The simulation
+ * counts are fpc_search_set_budget's, dead rows cost nothing under fpc_search_set_live_rows; this call is the rest.
+ * fast[g] != 0: game g's search of THIS ply is a fast search.  IN EFFECT for game g while the mask is set and fast[g] == 1;
+ * a full row (fast[g] == 0, or no mask) behaves bit for bit as without the call.
+ *   SELECTION  the forced-playout rule (fpc_search_set_forced) is not applied to game g, at any leaf k of a leaf-parallel
+ *              step; all other arithmetic is unchanged.
+ *   TARGET     the pruning is not applied to game g: fpc_search_targets reports the stored N_k, fpc_collect_tuples stores
+ *              N_k, fpc_search_play draws from powtab[N_k]; the solver's pick still overrides the draw.
+ *   RECORD     fpc_collect_tuples sets FPC_TUPLE_FAST in fpc_tuple::flags, whether or not forcing is in effect.
+ *   NOISE      is not the engine's business: k_tree_advance blends the noise inside the advance launch, before a mask can
+ *              be set.  The caller hands a fast row an all-zero gamma row (fpc_search_set_root_noise: a row whose sum is
+ *              not positive keeps its priors un-noised).
+ * Budgets, live rows, first-play urgency, the solver's statuses, virtual loss, fpc_search_results,
+ * fpc_search_grandchildren and sims_done do not change.
+ * The call sequence is fpc_search_set_budget's: the mask belongs to one ply; call it after fpc_search_begin,
+ * fpc_search_advance or fpc_search_advance_refill and before that search's first selection.  fast == NULL clears the mask,
+ * and so does every later fpc_search_begin / fpc_search_advance(_refill).  FPC_ESTATE as for fpc_search_set_budget.
+ * FPC_EINVAL (nothing uploaded, no state changed): null engine, n_games != the search's game count, an entry above 1.
+ * The first call allocates max_games bytes. */
+int fpc_search_set_fast_rows(fpc_engine *e, const uint8_t *fast /* host [n_games], nullable */, int n_games);
+
 /* ---- device-side move choice (opt-in): what a self-play ply does between the finished search and fpc_search_advance /
  * the next fpc_search_begin -- choose each game's move from the root's visit counts (alphazero.py:104-118), make it
  * (TakeAction, :119) and judge the game (GetGameResult, :120-123) -- as ONE launch (k_play_ply, one wave per game); the
@@ -557,7 +583,7 @@ int fpc_weights_pack_ms(fpc_engine *e, float *ms_out);
 typedef struct fpc_tuple {
   uint8_t sq[FPC_MAX_SQ];        /* root mailbox (piece bytes as in fpc_board) */
   uint8_t turn;                  /* side to move at the root */
-  uint8_t pad0;
+  uint8_t flags;                 /* FPC_TUPLE_* bits; 0 unless fpc_search_set_fast_rows marked the game */
   uint16_t n;                    /* number of (flat, visits) pairs */
   float z;                       /* filled by fpc_tuples_set_z */
   int32_t game, ply;             /* caller's game id and ply */
@@ -565,6 +591,8 @@ typedef struct fpc_tuple {
   uint16_t visits[FPC_TUPLE_MAXC];
   uint8_t pad1[44];
 } fpc_tuple;                     /* sizeof == 1280 */
+enum { FPC_TUPLE_FAST = 1 };     /* fpc_tuple::flags: the record comes from a fast search (fpc_search_set_fast_rows): its visit
+                                  * counts are the stored N_k of a short search without noise, no policy target for training */
 int fpc_tuples_reserve(fpc_engine *e, int capacity);    /* device buffer for `capacity` tuples; drops collected ones */
 int fpc_tuples_reset(fpc_engine *e);                    /* new episode: count = 0 */
 /* after a finished search (fpc_search_run / the select-expand loop): one tuple per game of that search,
@@ -623,6 +651,10 @@ int fpc_replay_read(fpc_engine *e, int ring, fpc_tuple *host_out, int first_slot
  * the host path's torch arithmetic; a record with n == 0, or whose visits sum to 0, gives a zero row), z_dev [n] f32.  Launched on the engine's
  * stream, which is synchronised before the call returns: any other stream may read the outputs afterwards. */
 int fpc_replay_batch(fpc_engine *e, int ring, const int *slot, int n, float *enc_dev, float *pi_dev, float *z_dev);
+/* fpc_replay_batch plus w_dev [n] f32, the record's policy-loss weight: 0.0f where the record has FPC_TUPLE_FAST, else
+ * 1.0f.  One launch, as fpc_replay_batch; enc_dev, pi_dev and z_dev are bit for bit what fpc_replay_batch writes for the
+ * same slots (a fast record's pi row is still decoded).  A null w_dev is FPC_EINVAL. */
+int fpc_replay_batch_w(fpc_engine *e, int ring, const int *slot, int n, float *enc_dev, float *pi_dev, float *z_dev, float *w_dev);
 
 /* ---- measurement hooks (bench.py) -------------------------------------------------------- */
 typedef struct fpc_stats {
